@@ -5,9 +5,17 @@ Workload (BASELINE.json configs[1]): Scene::Random (src/application.rs:497-565, 
 (inputs resident: the scene is committed once before timing).  1 ray = 1 world.hit call
 (application.rs:482), counted exactly on the device.
 
-  python bench.py                      # N=1, 3 timed frames after 1 warm-up
+  python bench.py                      # N=1, 3 timed frames after 1 warm-up: the headline figure alone
+  python bench.py --full               # ... plus delivery, parity, roofline, CPU baseline (and the N > 1 frame check)
+  python bench.py --dump-outputs DIR   # ... and the last timed step's pixels as DIR/<name>.npy
   python bench.py --gpus N             # N ranks, started by bench.py itself (hrt/launcher.py)
   python -m torch.distributed.run --nproc-per-node N bench.py --gpus N
+
+A plain run does what the headline needs and no more: scene set-up, one work-count frame (the exact rays of a
+step), the warm-up steps, the --steps timed steps, the --dump-outputs files if asked for, and the JSON line
+(metric, value, unit, ms_per_step, config, launch; parity, roofline and cpu_baseline are null).  Everything
+that takes runs of its own is behind --full: the per-frame delivery phase, the N > 1 gather and bit-identity
+check, the oracle parity band with the CPU baseline, and the instrumented roofline pass.
 
 Multi-GPU (north star: the image tiled across the GPUs of one node, host gather, no RCCL): one process
 per GPU; gloo carries only the control plane (barrier, max of the timings) and the host gather.  Without
@@ -18,8 +26,8 @@ N fresh ranks before anything touches the GPU, forwards rank 0's line and exits 
                    timed steps the shares are gathered to rank 0 and the frame is checked bit for bit
                    against a 1-GPU render of the whole frame.  Total work fixed: "scaling": "strong".
   --scaling weak   replicas: every rank renders the whole frame with its own next spp samples per pixel.
-Rank 0 prints ONE JSON line (contract in the task statement), with
-  parity       per-pixel L-inf of the timed frame against the CPU oracle on a band of rows spread over
+Rank 0 prints ONE JSON line (contract in the task statement), under --full with
+  parity      per-pixel L-inf of the timed frame against the CPU oracle on a band of rows spread over
                the frame (one GPU's share, --share N: on 16-px tiles spread over the share), at the frame's
                full spp, plus equality of the ray counts (the metric's own "per-pixel Linf vs CPU ref");
   roofline     the kernel's real bound, VALU instruction issue (PMC counts of this build from
@@ -83,6 +91,14 @@ def parse():
     ap.add_argument("--scaling", choices=["tiles", "weak"], default="tiles")
     ap.add_argument("--tile", type=int, default=tiling.TILE, help="tile pitch of the multi-GPU split")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what takes runs of its own: the per-frame delivery phase, the "
+                         "N > 1 gather and bit-identity check, the oracle parity band with the CPU baseline, and the "
+                         "instrumented roofline pass (a plain run prints the headline figure alone)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step rendered to DIR/<name>.npy (float32): 'frame' (H, W, 4) for one "
+                         "GPU's whole frame, else the rank's packed share; beyond the size budget a fixed seeded sample "
+                         "of its pixels")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU-baseline / parity sample")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU leg (and with it the parity band)")
     ap.add_argument("--no-parity", action="store_true", help="skip the oracle parity band (profiling runs)")
@@ -205,6 +221,28 @@ SCENE_DATA = {
     "earth_perlin": "seeded builder; the reference's assets/earthmap.jpg (tests/golden/earthmap_rgb8.png)",
     "final": "seeded builder; the reference's assets/earthmap.jpg (tests/golden/earthmap_rgb8.png)",
 }
+
+
+DUMP_BYTES = 64 * 1000 * 1000  # --dump-outputs: all ranks' files together stay under this
+DUMP_SEED = 0
+
+
+def dump_outputs(dirname, name, pixels, budget):
+    """--dump-outputs: `pixels` (the float32 RGBA pixels a caller of the timed path receives, any shape ending in 4)
+    to dirname/<name>.npy; an array beyond `budget` bytes as <name>_sample.npy, the pixels at a fixed seeded
+    choice of indices (sorted, the same for the same shape), shape (n, 4).  Returns the file written."""
+    import numpy as np
+
+    a = np.ascontiguousarray(pixels, dtype=np.float32)
+    room = budget - 4096  # the .npy header
+    if a.nbytes > room:
+        px = a.reshape(-1, 4)
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(px.shape[0], size=max(1, room // 16), replace=False))
+        a, name = px[pick], name + "_sample"
+    os.makedirs(dirname, exist_ok=True)
+    path = os.path.join(dirname, name + ".npy")
+    np.save(path, a)
+    return path
 
 
 def log(msg, all_ranks=False):
@@ -500,6 +538,8 @@ def delivery_phase(args, scene, cam, p, tiles, n_px, dev, stream, world, rank, b
 
 def main():
     args = parse()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -645,16 +685,26 @@ def main():
         seg_all, samples_all = float(seg_step), float(samples_step)
     value = seg_all * args.steps / dt / 1e6
 
-    # per-frame delivery (launch + D2H + placement into the host frame, pipelined): frame_ms beside the
-    # launch-only ms_per_step; for N > 1 the delivered frame is the host gather that the bit-identity
+    dumped = None
+    if args.dump_outputs:  # what the last timed step left in its output buffer, every rank its own
+        last = outs[(args.steps - 1) % n_str] if not turns else out
+        if world == 1 and share == 1:
+            dumped = dump_outputs(args.dump_outputs, "frame", last.view(H, W, 4).cpu().numpy(), DUMP_BYTES)
+        else:
+            name = "replica" if world > 1 and not tiled else "share"
+            dumped = dump_outputs(args.dump_outputs, name + (f"_rank{rank}" if world > 1 else ""),
+                                  last.view(n_px, 4).cpu().numpy(), DUMP_BYTES // world)
+
+    # --full: per-frame delivery (launch + D2H + placement into the host frame, pipelined): frame_ms beside
+    # the launch-only ms_per_step; for N > 1 the delivered frame is the host gather that the bit-identity
     # check below uses
     frame_check = None
     frame = None
     deliv = None
-    if not args.no_delivery and (world > 1 or share == 1):
+    if args.full and not args.no_delivery and (world > 1 or share == 1):
         deliv, frame = delivery_phase(args, scene, cam, p, tiles, n_px, dev, stream, world, rank, barrier, W, H,
                                       ms_per_step=dt / args.steps * 1e3)
-    if world > 1 and tiled:
+    if args.full and world > 1 and tiled:
         tg = time.perf_counter()
         if deliv is None:  # no delivery phase: gather the last timed frame's shares over gloo
             frame = tiling.gather_frame(out.cpu().numpy(), W, H, world, rank,
@@ -695,7 +745,7 @@ def main():
         frame = out.view(H, W, 4)
 
     cpu, parity = None, None
-    plan = parity_plan(world, rank, share, tiled, args)
+    plan = parity_plan(world, rank, share, tiled, args) if args.full else None
     if plan == "tiles":
         # one GPU's share (C4 / C5 config lines): the oracle on tiles spread over the share, and the metric's
         # L-inf on those tiles of the timed launch's packed output
@@ -732,7 +782,7 @@ def main():
     barrier()  # the other ranks wait for rank 0's CPU leg here, with no GPU work
 
     roofline = None
-    if rank == 0:
+    if rank == 0 and args.full:
         roofline = roofline_obj(args, scene, cam, bg, tiles, p, out.data_ptr(), stream.cuda_stream, launch_ms, seg_step, n_px,
                                 share=share)
 
@@ -772,6 +822,7 @@ def main():
                               if blob_info.walk_hot else "the whole walk stream in LDS"),
             },
             "launch": launch,
+            "full": args.full,
             "ranks": world,
             "devices": devices,
             "launcher": ("bench.py --gpus (hrt/launcher.py)" if os.environ.get("HRT_BENCH_SPAWNED")
@@ -784,6 +835,8 @@ def main():
             line["delivery"] = deliv
         if frame_check is not None:
             line["frame_check"] = frame_check
+        if dumped:
+            line["dump_outputs"] = dumped
         if knobs:
             line["knobs"] = knobs
         if args.one_device and world > 1:

@@ -36,7 +36,7 @@ fatal() { [ "$1" -ne 0 ] && [ "$1" -ne 1 ]; }
 bench_line() {  # bench_line <tag> <seconds> <bench args...>: the JSON line to <tag>.jsonl
   local tag=$1 secs=$2; shift 2
   echo "== $tag: bench.py $*" >> "$LOG"
-  timeout -k 10 "$secs" python -u bench.py "$@" >> "$OUT/$tag.jsonl" 2>> "$OUT/$tag.err"
+  timeout -k 10 "$secs" python -u bench.py --full "$@" >> "$OUT/$tag.jsonl" 2>> "$OUT/$tag.err"
   local rc=$?
   echo "== $tag exit $rc" >> "$LOG"
   return $rc
@@ -46,7 +46,7 @@ profile() {  # profile <tag> <preset> <W> <H> <spp> [share] [bench args...]
   local tag=$1 preset=$2 W=$3 H=$4 spp=$5; shift 5
   local share=1
   if [ $# -gt 0 ] && [[ $1 =~ ^[0-9]+$ ]]; then share=$1; shift; fi
-  local args="--preset $preset --width $W --height $H --spp $spp --share $share --steps 1 --warmup 1 --no-cpu-baseline --no-parity --no-delivery $*"
+  local args="--preset $preset --width $W --height $H --spp $spp --share $share --steps 1 --warmup 1 --full --no-cpu-baseline --no-parity --no-delivery $*"
   local rc=0
   export TMPDIR=/tmp
   pushd /tmp > /dev/null
@@ -82,13 +82,13 @@ step() {
     rehearsal)  # bench.py starts its own ranks (hrt/launcher.py): no torchrun
       local tag=$1; shift
       echo "== $tag: 2-rank rehearsal $*" >> "$LOG"
-      timeout -k 10 240 python -u bench.py --gpus 2 --one-device "$@" >> "$OUT/$tag.jsonl" 2>> "$OUT/$tag.err"
+      timeout -k 10 240 python -u bench.py --full --gpus 2 --one-device "$@" >> "$OUT/$tag.jsonl" 2>> "$OUT/$tag.err"
       local rc=$?; echo "== $tag exit $rc" >> "$LOG"; return $rc ;;
     rehearsaln)  # N ranks on one GPU (the N > 1 code paths: split, delivery, parity and CPU leg on the N-GPU frame)
       local tag=$1 n=$2; shift 2
       [ "$n" -le 4 ] || { echo "rehearsaln: at most 4 ranks" >> "$LOG"; return 2; }
       echo "== $tag: $n-rank rehearsal $*" >> "$LOG"
-      timeout -k 10 400 python -u bench.py --gpus "$n" --one-device "$@" >> "$OUT/$tag.jsonl" 2>> "$OUT/$tag.err"
+      timeout -k 10 400 python -u bench.py --full --gpus "$n" --one-device "$@" >> "$OUT/$tag.jsonl" 2>> "$OUT/$tag.err"
       local rc=$?; echo "== $tag exit $rc" >> "$LOG"; return $rc ;;
     rehtrace)  # kernel timeline of a concurrent 2-rank rehearsal: one rocprofv3 per rank (each rank its own
       # profiled program with the process-group variables set, so bench.py never spawns under the profiler's preload)
@@ -99,7 +99,7 @@ step() {
       for r in 0 1; do
         RANK=$r LOCAL_RANK=$r WORLD_SIZE=2 LOCAL_WORLD_SIZE=2 MASTER_ADDR=127.0.0.1 MASTER_PORT=$port \
           timeout -k 10 300 rocprofv3 --kernel-trace -d "$OUT/prof_${tag}/rank$r" -o run --output-format csv -- \
-          python3 "$ROOT/bench.py" --gpus 2 --one-device "$@" >> "$OUT/$tag.r$r.out" 2>> "$OUT/$tag.err" &
+          python3 "$ROOT/bench.py" --full --gpus 2 --one-device "$@" >> "$OUT/$tag.r$r.out" 2>> "$OUT/$tag.err" &
         pids+=($!)
       done
       for r in 0 1; do wait "${pids[$r]}" || rc=$?; done

@@ -88,6 +88,38 @@ def test_share_tiles_for_the_cpu_leg_spread_in_two_dimensions():
         assert len(picks) < 4 or span_x >= W / 2, (W, span_x)
 
 
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    """A plain run (no --full) does the headline's work alone; the legs with runs of their own are behind --full."""
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs == "" and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_whole_array_or_a_fixed_sample(tmp_path):
+    """--dump-outputs: an array within the budget is written whole as float32; a larger one as a seeded sample of
+    its pixels, the same pixels every time, within the budget on disk."""
+    import os
+
+    import numpy as np
+
+    frame = np.arange(36 * 64 * 4, dtype=np.float32).reshape(36, 64, 4)
+    p = bench.dump_outputs(str(tmp_path / "a"), "frame", frame, bench.DUMP_BYTES)
+    got = np.load(p)
+    assert os.path.basename(p) == "frame.npy" and got.dtype == np.float32 and np.array_equal(got, frame)
+    budget = 4096 + 1600  # room for 100 pixels beside the header
+    p1 = bench.dump_outputs(str(tmp_path / "b"), "frame", frame, budget)
+    p2 = bench.dump_outputs(str(tmp_path / "c"), "frame", frame + 0.0, budget)
+    s1, s2 = np.load(p1), np.load(p2)
+    assert os.path.basename(p1) == "frame_sample.npy" and s1.dtype == np.float32 and s1.shape == (100, 4)
+    assert np.array_equal(s1, s2) and os.path.getsize(p1) <= budget
+    px = (s1[:, 0] / 4).astype(int)  # pixel i holds 4i .. 4i+3
+    assert np.array_equal(s1, frame.reshape(-1, 4)[px]) and np.all(np.diff(px) > 0)
+    assert bench.DUMP_BYTES <= 64 * 1000 * 1000
+
+
 def test_stream_count_per_run():
     """--streams auto: two alternating streams for a GPU's share of C2 (short launches: the next step's grid fills
     the CUs the previous one's end frees), one for the whole frame and for C4's / C5's long share launches."""
