@@ -187,44 +187,96 @@ __device__ __forceinline__ void claim_work(const KParams& P, uint32_t lane, bool
   }
   /* head items [tile][8x8 block][head chunk][64 pixels] (a wave works through one block's chunks in a
    * row: its pixels' texels and partial sums stay in cache), then the tail items chunk-major
-   * [tail chunk][tile][8x8 block][64 pixels]; px = the padded pixel, then its tile (tiles padded to one
-   * stride: a division; else a binary search on pad_start) */
+   * [tail chunk][tile][8x8 block][64 pixels] (lane.h decode_item) */
   uint32_t chunk_head = P.chunk_head, pad_px = P.pad_px, tile_stride = P.tile_stride;
   if constexpr (RECOMPUTE) {
 #if defined(__HIP_DEVICE_COMPILE__)
     asm volatile("" : "+s"(chunk_head), "+s"(pad_px), "+s"(tile_stride));
 #endif
   }
-  uint32_t c, px;
-  if (w < P.head_items) {
-    const uint32_t g = w / (64u * chunk_head), rem = w - g * 64u * chunk_head;
-    c = rem >> 6;
-    px = g * 64u + (rem & 63u);
-  } else {
-    const uint32_t t = w - P.head_items, k = t / pad_px;
-    c = chunk_head + k;
-    px = t - k * pad_px;
-  }
-  uint32_t lo = 0;
-  if (tile_stride) {
-    lo = px / tile_stride;
-  } else {
-    uint32_t hi = P.n_tiles - 1;
-    while (lo < hi) {
-      uint32_t mid = (lo + hi + 1) >> 1;
-      if (P.tiles[mid].pad_start <= px) lo = mid; else hi = mid - 1;
+  decode_item(P, w, chunk_head, pad_px, tile_stride, has_item, it.pxy, it.slot, it.sample, it.sample_end);
+}
+
+/* The sphere kernel's claim (render_basic_kernel: chunks of 16 samples, so some lane claims in most passes).  The 64
+ * items of a claim share the tile, the 8x8 pixel block and the chunk (lane.h decode_block), so the wave decodes
+ * that ONCE, when it claims the block, into a descriptor, and a lane that takes an item finishes it from the
+ * descriptor and its w & 63 (lane.h take_from_block): no division, no tile load and no sample-range loop per lane.
+ * desc: the wave's current descriptor, its BLOCK_DESC_WORDS words in lanes 0 .. 7 of one VGPR (the SGPR file is
+ * full; written by per-lane selects when a block is claimed, read back by v_readlane when lanes take items).  The
+ * decode's divisors pass through an opaque copy (claim_work's RECOMPUTE), so no reciprocal is kept in registers.
+ * Every claim is a whole, 64-aligned block, to the end of the frame: the counter only ever moves by CLAIM_BLOCK, so
+ * P.claim_fine (HRT_CLAIM_FINE) does not apply to this kernel.  A claim can span two blocks: lanes of rank < avail
+ * take from the old descriptor before the new block overwrites it.  Retirement is claim_work's: a lane is exhausted
+ * on an item at or past P.total_work (a multiple of 64: a block is wholly inside or wholly past it), and a lane
+ * whose item is padding gets none and claims again. */
+__device__ __forceinline__ BlockDesc read_block_desc(uint32_t desc) {
+  BlockDesc d;
+  d.x0 = (uint32_t)__builtin_amdgcn_readlane((int)desc, 0);
+  d.y0 = (uint32_t)__builtin_amdgcn_readlane((int)desc, 1);
+  d.rw = (uint32_t)__builtin_amdgcn_readlane((int)desc, 2);
+  d.rh = (uint32_t)__builtin_amdgcn_readlane((int)desc, 3);
+  d.slot0 = (uint32_t)__builtin_amdgcn_readlane((int)desc, 4);
+  d.pitch = (uint32_t)__builtin_amdgcn_readlane((int)desc, 5);
+  d.s0 = (uint32_t)__builtin_amdgcn_readlane((int)desc, 6);
+  d.s1 = (uint32_t)__builtin_amdgcn_readlane((int)desc, 7);
+  return d;
+}
+/* lane k < 8 takes word k, the other lanes keep theirs (per-lane selects of wave-uniform values) */
+__device__ __forceinline__ uint32_t write_block_desc(uint32_t desc, uint32_t lane, const BlockDesc& d) {
+  uint32_t v = desc;
+  v = lane == 0u ? d.x0 : v;
+  v = lane == 1u ? d.y0 : v;
+  v = lane == 2u ? d.rw : v;
+  v = lane == 3u ? d.rh : v;
+  v = lane == 4u ? d.slot0 : v;
+  v = lane == 5u ? d.pitch : v;
+  v = lane == 6u ? d.s0 : v;
+  v = lane == 7u ? d.s1 : v;
+  return v;
+}
+__device__ __forceinline__ void claim_blocks(const KParams& P, uint32_t lane, bool& has_item, bool& exhausted, Item& it, WaveBlock& wb,
+                                             uint32_t& desc) {
+  const bool want = !has_item && !exhausted;
+  const unsigned long long want_mask = __ballot(want);
+  if (!want_mask) return;
+  const uint32_t cnt = (uint32_t)__popcll(want_mask);
+  const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(want_mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)want_mask, 0u));
+  const uint32_t avail = wb.end - wb.next; /* < 64: the rest of the wave's block, [next, end) inside it */
+  bool got = false, past = false;
+  if (avail) {
+    const bool mine = want && rank < avail;
+    if (wb.next >= P.total_work) {
+      past = mine;
+    } else {
+      const BlockDesc d = read_block_desc(desc);
+      if (mine) got = take_from_block(d, wb.next + rank, it.pxy, it.slot, it.sample, it.sample_end);
     }
   }
-  const G::TileDev T = P.tiles[lo];
-  const uint32_t q = px - T.pad_start;
-  const uint32_t blk = q >> 6, in = q & 63u;
-  const uint32_t lx = (blk % T.bw) * 8u + (in & 7u), ly = (blk / T.bw) * 8u + (in >> 3);
-  if (lx < T.w && ly < T.h) {
-    has_item = true;
-    it.pxy = (T.x + lx) | ((T.y + ly) << 16);
-    it.slot = c * P.n_out + (T.out_off + ly * T.w + lx);
-    chunk_range(P, c, it.sample, it.sample_end);
+  if (cnt > avail) { /* the next block (cnt <= 64 = CLAIM_BLOCK): the leader is the wanting lane of rank 0 */
+    const int leader = __ffsll((long long)want_mask) - 1;
+    uint32_t base = 0;
+    if (want && rank == 0u) base = atomicAdd(P.counter, CLAIM_BLOCK);
+    base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
+    const bool mine = want && rank >= avail;
+    if (base >= P.total_work) {
+      past = past || mine;
+    } else {
+      uint32_t chunk_head = P.chunk_head, pad_px = P.pad_px, tile_stride = P.tile_stride;
+#if defined(__HIP_DEVICE_COMPILE__)
+      asm volatile("" : "+s"(chunk_head), "+s"(pad_px), "+s"(tile_stride));
+#endif
+      BlockDesc d;
+      decode_block(P, base, chunk_head, pad_px, tile_stride, d);
+      desc = write_block_desc(desc, lane, d);
+      if (mine) got = take_from_block(d, base + (rank - avail), it.pxy, it.slot, it.sample, it.sample_end);
+    }
+    wb.next = base + (cnt - avail);
+    wb.end = base + CLAIM_BLOCK;
+  } else {
+    wb.next += cnt;
   }
+  has_item = has_item || got;
+  exhausted = exhausted || past;
 }
 
 /* A finished sample: add it to the chunk sum in order (application.rs:448); a finished chunk goes to

@@ -170,6 +170,114 @@ HRT_LANE_FI void chunk_range(const KParams& P, uint32_t k, uint32_t& s0, uint32_
   s1 = s + (P.chunk >> (1u + (j >> 1)));
 }
 
+/* ------------------------------------------------------------------ work-item decode
+ * Items are ordered [tile][8x8 block][head chunk][64 pixels], then the tail chunks' chunk-major
+ * [tail chunk][tile][8x8 block][64 pixels] (kernel_common.h claim_work).  pad_px, head_items, every tile's
+ * pad_start, tile_stride and total_work are multiples of 64, so the 64 items of a 64-aligned block share the
+ * tile, the 8x8 pixel block and the chunk; only w & 63 (the pixel inside the 8x8 block) differs.
+ * decode_item decodes one item from scratch; decode_block decodes what a block's items share, and
+ * take_from_block finishes one of its items.  tests/native/claim_decode.hip holds the two against each other
+ * for every item of a launch on the host.  chunk_head, pad_px, tile_stride: P's, or opaque copies of them (a
+ * kernel that wants their reciprocals computed at the claim instead of kept in registers). */
+
+/* the item w < P.total_work: valid is set when it is a pixel (left as it is when w falls into a tile's padding) */
+HRT_LANE_FI void decode_item(const KParams& P, uint32_t w, uint32_t chunk_head, uint32_t pad_px, uint32_t tile_stride,
+                             bool& valid, uint32_t& pxy, uint32_t& slot, uint32_t& s0, uint32_t& s1) {
+  /* px = the padded pixel, then its tile (tiles padded to one stride: a division; else a binary search
+   * on pad_start) */
+  uint32_t c, px;
+  if (w < P.head_items) {
+    const uint32_t g = w / (64u * chunk_head), rem = w - g * 64u * chunk_head;
+    c = rem >> 6;
+    px = g * 64u + (rem & 63u);
+  } else {
+    const uint32_t t = w - P.head_items, k = t / pad_px;
+    c = chunk_head + k;
+    px = t - k * pad_px;
+  }
+  uint32_t lo = 0;
+  if (tile_stride) {
+    lo = px / tile_stride;
+  } else {
+    uint32_t hi = P.n_tiles - 1;
+    while (lo < hi) {
+      uint32_t mid = (lo + hi + 1) >> 1;
+      if (P.tiles[mid].pad_start <= px) lo = mid; else hi = mid - 1;
+    }
+  }
+  const G::TileDev T = P.tiles[lo];
+  const uint32_t q = px - T.pad_start;
+  const uint32_t blk = q >> 6, in = q & 63u;
+  const uint32_t lx = (blk % T.bw) * 8u + (in & 7u), ly = (blk / T.bw) * 8u + (in >> 3);
+  if (lx < T.w && ly < T.h) {
+    valid = true;
+    pxy = (T.x + lx) | ((T.y + ly) << 16);
+    slot = c * P.n_out + (T.out_off + ly * T.w + lx);
+    chunk_range(P, c, s0, s1);
+  }
+}
+
+/* What the 64 items of a 64-aligned block share. */
+struct BlockDesc {
+  uint32_t x0, y0;   /* frame position of the 8x8 pixel block's corner */
+  uint32_t rw, rh;   /* the tile's columns / rows from that corner on (pixels at lx < rw, ly < rh exist); rh = 0 for a
+                        block past its tile (tiles padded to one stride) */
+  uint32_t slot0;    /* slot of the corner pixel in the block's chunk */
+  uint32_t pitch;    /* slots per pixel row (the tile's width) */
+  uint32_t s0, s1;   /* the chunk's samples */
+};
+constexpr int BLOCK_DESC_WORDS = 8;
+static_assert(sizeof(BlockDesc) == BLOCK_DESC_WORDS * sizeof(uint32_t), "BlockDesc is eight words");
+
+/* the block of items [w0, w0 + 64): w0 a multiple of 64, w0 < P.total_work */
+HRT_LANE_FI void decode_block(const KParams& P, uint32_t w0, uint32_t chunk_head, uint32_t pad_px, uint32_t tile_stride,
+                              BlockDesc& d) {
+  uint32_t c, px;
+  if (w0 < P.head_items) {
+    const uint32_t b = w0 >> 6, g = b / chunk_head;
+    c = b - g * chunk_head;
+    px = g * 64u;
+  } else {
+    const uint32_t t = w0 - P.head_items, k = t / pad_px;
+    c = chunk_head + k;
+    px = t - k * pad_px;
+  }
+  uint32_t lo = 0;
+  if (tile_stride) {
+    lo = px / tile_stride;
+  } else {
+    uint32_t hi = P.n_tiles - 1;
+    while (lo < hi) {
+      uint32_t mid = (lo + hi + 1) >> 1;
+      if (P.tiles[mid].pad_start <= px) lo = mid; else hi = mid - 1;
+    }
+  }
+  const G::TileDev T = P.tiles[lo];
+  const uint32_t blk = (px - T.pad_start) >> 6;
+  const uint32_t by = blk / T.bw, bx = blk - by * T.bw;
+  const uint32_t lx0 = bx * 8u, ly0 = by * 8u;
+  d.x0 = T.x + lx0;
+  d.y0 = T.y + ly0;
+  d.rw = T.w - lx0; /* bx < bw = ceil(w / 8): at least one column */
+  d.rh = ly0 < T.h ? T.h - ly0 : 0u;
+  d.slot0 = c * P.n_out + (T.out_off + ly0 * T.w + lx0);
+  d.pitch = T.w;
+  chunk_range(P, c, d.s0, d.s1);
+}
+
+/* item w of the block d describes (w - (w & 63) is the block's w0): false when it falls into padding */
+HRT_LANE_FI bool take_from_block(const BlockDesc& d, uint32_t w, uint32_t& pxy, uint32_t& slot, uint32_t& s0, uint32_t& s1) {
+  const uint32_t in = w & 63u, lx = in & 7u, ly = in >> 3;
+  if (lx < d.rw && ly < d.rh) {
+    pxy = (d.x0 + lx) | ((d.y0 + ly) << 16);
+    slot = d.slot0 + ly * d.pitch + lx;
+    s0 = d.s0;
+    s1 = d.s1;
+    return true;
+  }
+  return false;
+}
+
 /* per-lane work counters of the instrumented (COUNT) instantiation */
 struct Counts {
   uint32_t nodes, prims, tex;

@@ -953,7 +953,9 @@ hrt_status hrt_render_tiles_device(hrt_scene* s, const hrt_camera* cam, const hr
      * 1 / 4 M items measured +0.7 / -0.5 / -3% on C2 and -1 / -9 / -6% on a 1/8-frame share).  The
      * segment kernels claim per lane: a segment iteration is long, claims are rare, and with few items
      * per lane (Cornell 1024^2 x 128: 2) blocks unbalance the waves (-6%).
-     * HRT_CLAIM_FINE (A/B knob): claim the last that many items per lane, in every kernel */
+     * HRT_CLAIM_FINE (A/B knob): claim the last that many items per lane, in every kernel but the sphere
+     * kernel, which decodes a claim once per 64-aligned block and so only ever claims whole blocks
+     * (kernel_common.h claim_blocks) */
     const bool sphere_kernel = (!pl.full && !pl.fast && !pl.general) || pl.gwalk; /* block claims */
     const char* cf = knob_env("HRT_CLAIM_FINE");
     const uint64_t work = pad * n_chunks;

@@ -22,6 +22,11 @@ using namespace hrt::kern;
 #define HRT_HEAVY_WAVES 4 /* HEAVY: the out-of-line texture calls spill live registers at 80 VGPRs (6 waves) */
 #endif
 
+#ifndef HRT_CLAIM_BLOCKS
+#define HRT_CLAIM_BLOCKS 1 /* the wave decodes a claimed block once (kernel_common.h claim_blocks); 0: every lane decodes
+                              its own item (claim_work, for A/B) */
+#endif
+
 namespace {
 
 template <bool HEAVY>
@@ -94,6 +99,9 @@ void render_basic_kernel(KParams P) {
   bool setup = false;   /* the lane's next segment needs its ray set up (a new sample, or a scattered ray) */
   Item it{0u, 0u, 0u, 0u};
   WaveBlock wb{0u, 0u};
+#if HRT_CLAIM_BLOCKS
+  uint32_t desc = 0u; /* the wave's block descriptor, in lanes 0 .. 7 (kernel_common.h claim_blocks) */
+#endif
   Vec3 sum = v3(0.0f, 0.0f, 0.0f);
   PathState ps;
   init_path_state(ps);
@@ -126,7 +134,11 @@ void render_basic_kernel(KParams P) {
   for (;;) {
     /* lanes without work claim it; lanes with work but no segment in flight start a sample */
     const bool had_item = has_item;
+#if HRT_CLAIM_BLOCKS
+    claim_blocks(P, lane, has_item, exhausted, it, wb, desc);
+#else
     claim_work(P, lane, has_item, exhausted, it, wb);
+#endif
     if (has_item && !had_item) *slot_lds = it.slot;
     if (!__any(has_item || !exhausted)) break;
     if (has_item && !walking) {
