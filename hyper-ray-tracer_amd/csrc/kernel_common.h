@@ -121,7 +121,7 @@ __device__ __forceinline__ void stage_scene(const KParams& P, float4* lds, const
 }
 
 /* A lane's current work item: one pixel and a chunk [sample, sample_end) of its samples.  slot: where
- * the chunk's result goes, P.out[slot] (one chunk) or P.partial[slot] = [chunk][n_out] (the host checks
+ * the chunk's result goes, P.out[slot] (P.direct_out: one chunk, a frame) or P.partial[slot] = [chunk][n_out] (the host checks
  * n_chunks x n_out < 2^32); the chunk is first iff sample_end <= P.chunk (lane.h chunk_plan). */
 struct Item {
   uint32_t pxy; /* px | py << 16 */
@@ -286,7 +286,7 @@ __device__ __forceinline__ void finish_sample(const KParams& P, Item& it, Vec3& 
   sum = sum + rad;
   n_samples++;
   if (++it.sample == it.sample_end) {
-    if (P.n_chunks == 1) {
+    if (P.direct_out == 1) {
       P.out[it.slot] = make_float4(sqrtf(sum.x * scale), sqrtf(sum.y * scale), sqrtf(sum.z * scale), 1.0f);
       n_pixels++;
     } else {

@@ -65,7 +65,11 @@ struct KParams {
   uint32_t claim_fine; /* work items from here on are claimed one per lane (kernel_common.h claim_work) */
   unsigned long long* stats; /* segments, samples, pixels, then (COUNT builds) nodes, prims, tex */
   /* sample chunks: a work item is (pixel, chunk of consecutive samples); lane.h chunk_range */
-  uint32_t chunk, n_chunks, n_out;
+  uint32_t chunk;
+  uint32_t direct_out; /* wave-uniform, resolved by the host: 1 = a finished chunk is the finished pixel and goes to
+                          out[slot] as sqrt(sum / spp) (a one-chunk render); 0 = its raw sum goes to partial[slot]
+                          (several chunks, or a pass of an accumulator, hrt_accum_add, whatever its chunk count) */
+  uint32_t n_out;
   uint32_t chunk_head, chunk_first; /* head chunks (the first holds chunk_first samples, the rest `chunk`) */
   uint32_t pad_px;                  /* padded pixels of the call's tiles */
   uint32_t head_items;              /* pad_px x chunk_head: the head chunks' items come first (claim_work) */
@@ -77,7 +81,7 @@ struct KParams {
   uint32_t walk_cap;   /* watchdog: more consecutive walk-loop iterations than any valid walk needs */
   uint32_t motion_uniform; /* every moving sphere has time0 = motion_t0, time1 - time0 = motion_span */
   float motion_t0, motion_span;
-  float4* partial; /* [n_chunks][n_out] chunk sums (n_chunks > 1): a claim's 64 lanes write one chunk of 64
+  float4* partial; /* [n_chunks][n_out] chunk sums (direct_out = 0): a claim's 64 lanes write one chunk of 64
                       consecutive pixels, whole cache lines (r05; [n_out][n_chunks] wrote 2.35x the sums' bytes
                       on Final, 16-B writes into lines a wave completes only chunks later) */
   /* sphere-scene walk stream (layout.h; render_basic_kernel under CULL_EXACT) */
@@ -92,6 +96,7 @@ struct KParams {
   uint32_t walk_half;  /* the walk stream's node-part split (layout.h WALK_SPLIT_HALF) or 16 */
   uint32_t walk_c16;   /* 16-B node parts (layout.h WALK_C16): walk_end is then the node count */
   uint32_t walk_pbase; /* walk_c16: byte offset of the payloads */
+  uint32_t n_chunks;   /* chunks per pixel (host side and the lane simulator; the kernels read direct_out) */
 };
 
 /* Sample-chunk size: spp <= cmin keeps one work item per pixel (the reference's sequential sum), larger

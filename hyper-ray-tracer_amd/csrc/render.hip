@@ -32,6 +32,7 @@
 #include <string>
 #include <vector>
 
+#include "accum.h"
 #include "kernel_common.h"
 
 using namespace hrt;
@@ -209,7 +210,7 @@ void render_full_kernel(KParams P) {
         sum = sum + ps.rad;
         sample_done = true;
         if (++it.sample == it.sample_end) {
-          if (P.n_chunks == 1)
+          if (P.direct_out == 1)
             P.out[it.slot] = make_float4(sqrtf(sum.x * scale), sqrtf(sum.y * scale), sqrtf(sum.z * scale), 1.0f);
           else
             P.partial[it.slot] = make_float4(sum.x, sum.y, sum.z, 0.0f);
@@ -247,6 +248,53 @@ __global__ __launch_bounds__(256) void reduce_chunks(const float4* __restrict__ 
       sum = sum + v3(b.x, b.y, b.z);
     }
     out[i] = make_float4(sqrtf(sum.x * scale), sqrtf(sum.y * scale), sqrtf(sum.z * scale), 1.0f);
+  }
+}
+
+/* ---- the sample accumulator's kernels (hrt_accum; arithmetic: accum.h).  Plain streaming kernels: a grid-stride
+ * loop over pixels, one 16-B load or store per lane and array (consecutive lanes, consecutive float4s). */
+constexpr uint32_t STREAM_MAX_BLOCKS = 4096; /* reduce_chunks' cap: larger frames take further trips of the loop */
+inline uint32_t stream_blocks(size_t n) { return (uint32_t)std::min<size_t>((n + 255) / 256, STREAM_MAX_BLOCKS); }
+
+/* a resolved pixel to out[i]: RGBA f32 with alpha 1, or 4 x u8 with alpha 255 */
+template <int FORMAT>
+__host__ __device__ inline void store_resolved(void* out, size_t i, Vec3 acc, float scale) {
+  const Vec3 px = accum::resolve_f32(acc, scale);
+  if constexpr (FORMAT == HRT_ACCUM_F32) static_cast<float4*>(out)[i] = make_float4(px.x, px.y, px.z, 1.0f);
+  else static_cast<uint32_t*>(out)[i] = accum::resolve_rgba8(px);
+}
+
+/* acc[i] += the pass sum of partial[.][i]; FORMAT >= 0: the frame after the pass goes to out in the same trip
+ * (scale = 1 / the samples then held), so a preview after every pass is this one kernel after the megakernel */
+template <int FORMAT>
+__host__ __device__ inline void accumulate_pixel(const float4* partial, float4* acc, size_t n, uint32_t n_chunks, float scale,
+                                                 void* out, size_t i) {
+  const float4 a = acc[i];
+  const Vec3 sum = accum::add_pass(v3(a.x, a.y, a.z), accum::pass_sum(partial, n_chunks, n, i));
+  acc[i] = make_float4(sum.x, sum.y, sum.z, 0.0f);
+  if constexpr (FORMAT >= 0) store_resolved<FORMAT>(out, i, sum, scale);
+}
+template <int FORMAT>
+__global__ __launch_bounds__(256) void accumulate_chunks(const float4* __restrict__ partial, float4* __restrict__ acc, size_t n,
+                                                         uint32_t n_chunks, float scale, void* __restrict__ out) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    accumulate_pixel<FORMAT>(partial, acc, n, n_chunks, scale, out, i);
+}
+
+/* dst += src */
+__global__ __launch_bounds__(256) void accum_merge(float4* __restrict__ dst, const float4* __restrict__ src, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const float4 a = dst[i], b = src[i];
+    const Vec3 sum = accum::add_pass(v3(a.x, a.y, a.z), v3(b.x, b.y, b.z));
+    dst[i] = make_float4(sum.x, sum.y, sum.z, 0.0f);
+  }
+}
+
+template <int FORMAT>
+__global__ __launch_bounds__(256) void accum_resolve(const float4* __restrict__ acc, size_t n, float scale, void* __restrict__ out) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const float4 a = acc[i];
+    store_resolved<FORMAT>(out, i, v3(a.x, a.y, a.z), scale);
   }
 }
 
@@ -843,6 +891,326 @@ struct DevBuf {
 
 }  // namespace hrt
 
+namespace {
+
+/* Where the sums of a launch go: into a frame (hrt_render_tiles_device: d_rgba = sqrt(sum / spp)), or added to an
+ * accumulator's raw sums (hrt_accum_add: d_acc), optionally with the accumulated frame resolved to d_preview by
+ * the kernel that adds the pass. */
+struct SumsDest {
+  float* d_rgba = nullptr;
+  float4* d_acc = nullptr;
+  int preview = -1;          /* HRT_ACCUM_* format of d_preview, -1: none */
+  void* d_preview = nullptr;
+  float preview_scale = 0.0f; /* 1 / the accumulator's samples after this pass */
+};
+
+template <int FORMAT>
+void launch_accumulate(const float4* partial, float4* acc, size_t n, uint32_t n_chunks, float scale, void* out,
+                       hipStream_t stream) {
+  hipLaunchKernelGGL((accumulate_chunks<FORMAT>), dim3(stream_blocks(n)), dim3(256), 0, stream, partial, acc, n, n_chunks,
+                     scale, out);
+  hip_check(hipGetLastError(), "accumulate_chunks launch");
+}
+void launch_accumulate(int format, const float4* partial, float4* acc, size_t n, uint32_t n_chunks, float scale, void* out,
+                       hipStream_t stream) {
+  if (format == HRT_ACCUM_F32) launch_accumulate<HRT_ACCUM_F32>(partial, acc, n, n_chunks, scale, out, stream);
+  else if (format == HRT_ACCUM_RGBA8) launch_accumulate<HRT_ACCUM_RGBA8>(partial, acc, n, n_chunks, scale, out, stream);
+  else launch_accumulate<-1>(partial, acc, n, n_chunks, 0.0f, nullptr, stream);
+}
+
+/* One render launch of a tile set, shared by every entry point up to where its sums go (dst): argument checks, the
+ * chunk schedule, tile table and stride, the scratch slot, plan, claim set-up, the megakernel, then reduce_chunks
+ * (a frame) or accumulate_chunks (an accumulator), the stats copy-back and the slot's error word.  *launched is
+ * set once the megakernel has been enqueued (an error after that leaves dst partly written). */
+void render_launch(hrt_scene* s, const hrt_camera* cam, const hrt_render_params* p, const hrt_tile* tiles, uint32_t n_tiles,
+                   const SumsDest& dst, void* stream_, hrt_render_stats* stats, bool* launched) {
+  float* const d_rgba = dst.d_rgba;
+  const bool raw = dst.d_acc != nullptr; /* the raw sums are wanted: every chunk's go to the slot's partial buffer */
+  if (!s->committed || !s->d_blob) throw HipError{HRT_ERR_STATE, "scene not committed"};
+  check_render_args(cam, p);
+  /* sample chunks (lane.h sample_chunk): they bound the frame's tail: the last items of a launch run
+   * alone, and a pixel whose paths bounce 50 times makes a long item (a 1/8-frame share of C2: chunks
+   * of 8 / 16 / 24 / 32 / 63 samples gave 12590 / 12330 / 11628 / 10796 / 9270 Mrays/s; the whole
+   * frame 14243 / 14489 / 14489 / 14338 / 13930).  The rule depends on spp and
+   * the scene's feature class only, so every tile split sums a pixel's samples in the same chunks. */
+  const uint32_t spp = p->samples;
+  uint32_t chunk = 0, n_head = 0, first = 0, n_tail = 0;
+  chunk_schedule(s, p, chunk, n_head, first, n_tail);
+  const uint32_t n_chunks = n_head + n_tail;
+  std::vector<G::TileDev> td(n_tiles);
+  uint64_t pad = 0, outp = 0;
+  for (uint32_t i = 0; i < n_tiles; i++) {
+    const hrt_tile& t = tiles[i];
+    if (t.w == 0 || t.h == 0 || (uint64_t)t.x + t.w > p->width || (uint64_t)t.y + t.h > p->height)
+      throw HipError{HRT_ERR_INVALID_ARG, "tile outside the image"};
+    uint32_t bw = (t.w + 7) / 8, bh = (t.h + 7) / 8;
+    td[i] = G::TileDev{t.x, t.y, t.w, t.h, bw, (uint32_t)pad, (uint32_t)outp, 0};
+    pad += (uint64_t)bw * bh * 64; /* padded pixels (items: pad x n_chunks, chunk-major) */
+    outp += (uint64_t)t.w * t.h;
+  }
+  /* Many tiles (a rank's share of the 16-px grid: 4080 tiles at 2 GPUs): a claim's binary search over
+   * the tile table was a dozen dependent global loads.  When padding every tile to the largest one's
+   * item count costs at most 1/8 more (idle) items, tile = item / stride instead (share of 2 / 8 on C2:
+   * DESIGN.md section 6.1). */
+  uint32_t stride = 0;
+  if (n_tiles > 1) {
+    uint64_t mx = 0;
+    for (uint32_t i = 0; i < n_tiles; i++) mx = std::max<uint64_t>(mx, (uint64_t)((td[i].w + 7) / 8) * ((td[i].h + 7) / 8) * 64);
+    const char* ts = knob_env("HRT_TILE_STRIDE"); /* A/B knob: "0" keeps the binary search */
+    if (mx * n_tiles <= pad + pad / 8 && mx * n_tiles * n_chunks < 0xF0000000ull && !(ts && strcmp(ts, "0") == 0)) {
+      stride = (uint32_t)mx;
+      for (uint32_t i = 0; i < n_tiles; i++) td[i].pad_start = i * stride;
+      pad = mx * n_tiles;
+    }
+  }
+  /* work items and Item.slot (pixel x n_chunks + chunk < pad x n_chunks) are 32-bit */
+  /* headroom: waves claim blocks of CLAIM_BLOCK items past the end before they retire */
+  if (pad * n_chunks >= 0xF0000000ull) throw HipError{HRT_ERR_UNSUPPORTED, "more than 3.75G pixel x sample-chunk items in one call"};
+  hipStream_t stream = (hipStream_t)stream_;
+  DeviceGuard dg(s->device);
+  /* scratch slot: device [counter u32 | pad | stats 8 x u64 | pad to HDR | tiles], pinned host [stats | tiles] */
+  std::lock_guard<std::mutex> lock(*static_cast<std::mutex*>(s->slot_mutex));
+  /* an earlier launch whose walks the watchdog killed is reported by the first call that sees its
+   * copied-back error word (every launch copies it, with or without stats) */
+  for (auto& other : s->slots)
+    if (other.used && hipEventQuery((hipEvent_t)other.event) == hipSuccess) take_slot_error(other);
+  hrt_scene::Slot& sl = s->slots[s->next_slot++ % hrt_scene::N_SLOTS];
+  if (sl.used) {
+    hip_check(hipEventSynchronize((hipEvent_t)sl.event), "hipEventSynchronize(slot)");
+    take_slot_error(sl);
+  }
+  size_t tiles_bytes = n_tiles * sizeof(G::TileDev);
+  const size_t partial_bytes = n_chunks > 1 || raw ? (size_t)n_chunks * outp * sizeof(float4) : 0;
+  auto grow = [&](hrt_scene::Slot& g, bool partial) {
+    if (tiles_bytes > g.tiles_cap) {
+      if (g.d_mem) hip_check(hipFree(g.d_mem), "hipFree(slot)");
+      if (g.h_tiles) hip_check(hipHostFree(g.h_tiles), "hipHostFree(slot)");
+      g.d_mem = g.h_tiles = nullptr;
+      g.tiles_cap = 0;
+      size_t cap = std::max<size_t>(tiles_bytes, 64 * sizeof(G::TileDev));
+      hip_check(hipMalloc(&g.d_mem, SLOT_HDR + cap), "hipMalloc(slot)");
+      hip_check(hipHostMalloc(&g.h_tiles, SLOT_HDR + cap, hipHostMallocDefault), "hipHostMalloc(slot)");
+      g.tiles_cap = cap;
+    }
+    if (partial && partial_bytes > g.partial_cap) {
+      if (g.d_partial) hip_check(hipFree(g.d_partial), "hipFree(partial)");
+      g.d_partial = nullptr;
+      g.partial_cap = 0;
+      hip_check(hipMalloc(&g.d_partial, partial_bytes), "hipMalloc(partial)");
+      g.partial_cap = partial_bytes;
+    }
+  };
+  /* slots never launched are grown with this one, so the next calls (e.g. a timed loop that keeps
+   * several launches in flight) do not allocate pinned and device memory between launches.  Their
+   * partial-sum buffers (a pixel's chunk sums: 1 GB for C2's 32 chunks) only when this call is
+   * asynchronous (no stats): a synchronous caller (hrt_render, a progressive batch with stats) never
+   * has a second launch in flight, and would otherwise hold N_SLOTS such buffers. */
+  const bool first_growth = tiles_bytes > sl.tiles_cap || partial_bytes > sl.partial_cap;
+  grow(sl, true);
+  if (first_growth)
+    for (auto& other : s->slots)
+      if (&other != &sl && !other.used) grow(other, stats == nullptr);
+  void* scratch = sl.d_mem;
+  memcpy((uint8_t*)sl.h_tiles + SLOT_HDR, td.data(), tiles_bytes);
+  hip_check(hipMemsetAsync(scratch, 0, SLOT_HDR, stream), "hipMemsetAsync");
+  hip_check(hipMemcpyAsync((uint8_t*)scratch + SLOT_HDR, (uint8_t*)sl.h_tiles + SLOT_HDR, tiles_bytes, hipMemcpyHostToDevice,
+                           stream), "hipMemcpyAsync(tiles)");
+  const Plan pl = plan(s, cam, p->flags);
+  KParams kp = scene_params(s, cam, p, pl);
+  kp.tiles = (const G::TileDev*)((uint8_t*)scratch + SLOT_HDR);
+  kp.n_tiles = n_tiles;
+  kp.total_work = (uint32_t)(pad * n_chunks);
+  kp.pad_px = (uint32_t)pad;
+  kp.head_items = (uint32_t)(pad * n_head);
+  kp.tile_stride = stride;
+  /* the sphere kernel claims blocks of items to the end: its passes are short, and per-lane claims
+   * made them wait on the contended counter (r02y: +12% on C2; per-lane claims for the last 0.26 /
+   * 1 / 4 M items measured +0.7 / -0.5 / -3% on C2 and -1 / -9 / -6% on a 1/8-frame share).  The
+   * segment kernels claim per lane: a segment iteration is long, claims are rare, and with few items
+   * per lane (Cornell 1024^2 x 128: 2) blocks unbalance the waves (-6%).
+   * HRT_CLAIM_FINE (A/B knob): claim the last that many items per lane, in every kernel but the sphere
+   * kernel, which decodes a claim once per 64-aligned block and so only ever claims whole blocks
+   * (kernel_common.h claim_blocks) */
+  const bool sphere_kernel = (!pl.full && !pl.fast && !pl.general) || pl.gwalk; /* block claims */
+  const char* cf = knob_env("HRT_CLAIM_FINE");
+  const uint64_t work = pad * n_chunks;
+  const uint64_t fine = cf ? strtoull(cf, nullptr, 10) : (sphere_kernel ? 0u : work);
+  kp.claim_fine = (uint32_t)(work > fine ? work - fine : 0);
+  kp.out = (float4*)d_rgba;
+  kp.counter = (uint32_t*)scratch;
+  kp.stats = (unsigned long long*)((uint8_t*)scratch + 8);
+  kp.chunk = chunk;
+  kp.n_chunks = n_chunks;
+  kp.direct_out = n_chunks == 1 && !raw ? 1u : 0u;
+  kp.chunk_head = n_head;
+  kp.chunk_first = first;
+  kp.n_out = (uint32_t)outp;
+  kp.partial = (float4*)sl.d_partial;
+  if (p->flags & HRT_RENDER_COUNT_WORK) launch_any<true>(s, pl, kp, stream);
+  else launch_any<false>(s, pl, kp, stream);
+  launch_knobs(s);
+  if (launched) *launched = true;
+  if (raw) {
+    launch_accumulate(dst.preview, (const float4*)sl.d_partial, dst.d_acc, (size_t)outp, n_chunks, dst.preview_scale,
+                      dst.d_preview, stream);
+  } else if (n_chunks > 1) {
+    uint32_t blocks = (uint32_t)std::min<uint64_t>((outp + 255) / 256, 4096);
+    hipLaunchKernelGGL(reduce_chunks, dim3(blocks), dim3(256), 0, stream, (const float4*)sl.d_partial,
+                       (float4*)d_rgba, (uint32_t)outp, n_chunks, spp);
+    hip_check(hipGetLastError(), "reduce_chunks launch");
+  }
+  /* the stats words and the watchdog's error word (h[12]) come back after EVERY launch, so a killed
+   * frame is reported even when the caller asked for no stats (take_slot_error) */
+  unsigned long long* h = (unsigned long long*)sl.h_tiles;
+  hip_check(hipMemcpyAsync(h, (uint8_t*)scratch + 8, 136, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(stats)");
+  hip_check(hipEventRecord((hipEvent_t)sl.event, stream), "hipEventRecord(slot)");
+  sl.used = true;
+  if (stats) {
+    hip_check(hipEventSynchronize((hipEvent_t)sl.event), "hipEventSynchronize(stats)");
+    take_slot_error(sl);
+    stats->segments = h[0];
+    stats->samples = h[1];
+    stats->pixels = h[2];
+    stats->node_visits = h[3];
+    stats->prim_tests = h[4];
+    stats->tex_evals = h[5];
+    stats->walk_slots = h[6];
+    stats->shade_slots = h[7];
+    stats->prim_slots = h[8];
+    for (int k = 0; k < 3; k++) stats->phase_cycles[k] = h[9 + k];
+    stats->park_slots = h[13];
+    stats->wait_slots = h[14];
+    stats->leaf_cycles = h[15];
+    stats->walk_steps = h[16];
+  }
+}
+
+/* the sorted, disjoint, coalesced [begin, end) sample ranges an accumulator holds (ends up to 2^32) */
+struct SampleRange {
+  uint64_t begin, end;
+};
+bool ranges_overlap(const std::vector<SampleRange>& have, const SampleRange& r) {
+  for (const SampleRange& h : have)
+    if (r.begin < h.end && h.begin < r.end) return true;
+  return false;
+}
+/* r is non-empty and overlaps nothing in `have` */
+void ranges_insert(std::vector<SampleRange>& have, SampleRange r) {
+  size_t at = 0;
+  while (at < have.size() && have[at].begin < r.begin) at++;
+  have.insert(have.begin() + at, r);
+  for (size_t i = 0; i + 1 < have.size();) {
+    if (have[i].end == have[i + 1].begin) {
+      have[i].end = have[i + 1].end;
+      have.erase(have.begin() + i + 1);
+    } else {
+      i++;
+    }
+  }
+}
+uint64_t ranges_total(const std::vector<SampleRange>& have) {
+  uint64_t n = 0;
+  for (const SampleRange& h : have) n += h.end - h.begin;
+  return n;
+}
+
+/* what makes two passes samples of the same frame: everything of (camera, params) but samples and sample_offset */
+struct FrameIdentity {
+  hrt_camera cam;
+  uint32_t width, height, max_depth, flags;
+  float t_min, background[3];
+  uint64_t seed;
+};
+FrameIdentity frame_identity(const hrt_camera* cam, const hrt_render_params* p) {
+  FrameIdentity id;
+  memset(&id, 0, sizeof(id));
+  id.cam = *cam;
+  id.width = p->width;
+  id.height = p->height;
+  id.max_depth = p->max_depth;
+  id.flags = p->flags;
+  id.t_min = p->t_min;
+  for (int k = 0; k < 3; k++) id.background[k] = p->background[k];
+  id.seed = p->seed;
+  return id;
+}
+bool same_identity(const FrameIdentity& a, const FrameIdentity& b) {
+  return memcmp(&a.cam, &b.cam, sizeof(hrt_camera)) == 0 && a.width == b.width && a.height == b.height &&
+         a.max_depth == b.max_depth && a.flags == b.flags && memcmp(&a.t_min, &b.t_min, sizeof(float)) == 0 &&
+         memcmp(a.background, b.background, sizeof(a.background)) == 0 && a.seed == b.seed;
+}
+
+}  // namespace
+
+struct hrt_accum {
+  hrt_scene* scene = nullptr;
+  int device = -1;
+  uint32_t width = 0, height = 0;
+  std::vector<hrt_tile> tiles;
+  size_t n_px = 0;
+  float4* d_acc = nullptr; /* n_px raw sums (x, y, z; w = 0), packed as the tiles are */
+  bool has_identity = false;
+  FrameIdentity identity;
+  std::vector<SampleRange> ranges;
+  bool invalid = false; /* a pass was stopped by the walk watchdog: the sums are incomplete until a reset */
+};
+
+namespace {
+
+void accum_usable(const hrt_accum* a) {
+  if (a->invalid) throw HipError{HRT_ERR_STATE, "the accumulator holds an incomplete pass (walk watchdog): reset it"};
+}
+void accum_format(int32_t format) {
+  if (format != HRT_ACCUM_F32 && format != HRT_ACCUM_RGBA8) throw HipError{HRT_ERR_INVALID_ARG, "unknown HRT_ACCUM_* format"};
+}
+void check_identity(const hrt_accum* a, const FrameIdentity& id) {
+  if (id.width != a->width || id.height != a->height)
+    throw HipError{HRT_ERR_INVALID_ARG, "the params' width and height are not the accumulator's"};
+  if (a->has_identity && !same_identity(a->identity, id))
+    throw HipError{HRT_ERR_INVALID_ARG, "another frame identity (camera, max_depth, flags, t_min, background, seed) than the accumulator's"};
+}
+void check_range(const std::vector<SampleRange>& have, const SampleRange& r) {
+  if (r.begin >= r.end || r.end > (1ull << 32)) throw HipError{HRT_ERR_INVALID_ARG, "empty sample range, or one that ends past 2^32"};
+  if (ranges_overlap(have, r)) throw HipError{HRT_ERR_INVALID_ARG, "the sample range overlaps samples the accumulator holds"};
+}
+void launch_resolve(const hrt_accum* a, int32_t format, void* d_out, hipStream_t stream) {
+  const float scale = accum::resolve_scale(ranges_total(a->ranges));
+  if (format == HRT_ACCUM_F32)
+    hipLaunchKernelGGL((accum_resolve<HRT_ACCUM_F32>), dim3(stream_blocks(a->n_px)), dim3(256), 0, stream, (const float4*)a->d_acc,
+                       a->n_px, scale, d_out);
+  else
+    hipLaunchKernelGGL((accum_resolve<HRT_ACCUM_RGBA8>), dim3(stream_blocks(a->n_px)), dim3(256), 0, stream, (const float4*)a->d_acc,
+                       a->n_px, scale, d_out);
+  hip_check(hipGetLastError(), "accum_resolve launch");
+}
+
+/* hrt_accum_add / hrt_accum_add_resolve: checks first (nothing changes on an error), then the shared launch */
+void accum_add(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, int32_t format, void* d_out, void* stream,
+               hrt_render_stats* stats) {
+  accum_usable(a);
+  const FrameIdentity id = frame_identity(cam, p);
+  check_identity(a, id);
+  const SampleRange r{p->sample_offset, (uint64_t)p->sample_offset + p->samples};
+  if (p->samples != 0) check_range(a->ranges, r); /* samples = 0: check_render_args reports it */
+  SumsDest dst;
+  dst.d_acc = a->d_acc;
+  dst.preview = d_out ? format : -1;
+  dst.d_preview = d_out;
+  dst.preview_scale = accum::resolve_scale(ranges_total(a->ranges) + p->samples);
+  bool launched = false;
+  try {
+    render_launch(a->scene, cam, p, a->tiles.data(), (uint32_t)a->tiles.size(), dst, stream, stats, &launched);
+  } catch (...) {
+    if (launched) a->invalid = true; /* the pass is (partly) in the sums and cannot be taken out again */
+    throw;
+  }
+  a->identity = id;
+  a->has_identity = true;
+  ranges_insert(a->ranges, r);
+}
+
+}  // namespace
+
 extern "C" {
 
 hrt_status hrt_render_tiles_device(hrt_scene* s, const hrt_camera* cam, const hrt_render_params* p,
@@ -851,158 +1219,9 @@ hrt_status hrt_render_tiles_device(hrt_scene* s, const hrt_camera* cam, const hr
   return hguard([&] {
     if (!s || !cam || !p || !tiles || !d_rgba || n_tiles == 0)
       throw HipError{HRT_ERR_INVALID_ARG, "hrt_render_tiles_device: null argument"};
-    if (!s->committed || !s->d_blob) throw HipError{HRT_ERR_STATE, "scene not committed"};
-    check_render_args(cam, p);
-    /* sample chunks (lane.h sample_chunk): they bound the frame's tail: the last items of a launch run
-     * alone, and a pixel whose paths bounce 50 times makes a long item (a 1/8-frame share of C2: chunks
-     * of 8 / 16 / 24 / 32 / 63 samples gave 12590 / 12330 / 11628 / 10796 / 9270 Mrays/s; the whole
-     * frame 14243 / 14489 / 14489 / 14338 / 13930).  The rule depends on spp and
-     * the scene's feature class only, so every tile split sums a pixel's samples in the same chunks. */
-    const uint32_t spp = p->samples;
-    uint32_t chunk = 0, n_head = 0, first = 0, n_tail = 0;
-    chunk_schedule(s, p, chunk, n_head, first, n_tail);
-    const uint32_t n_chunks = n_head + n_tail;
-    std::vector<G::TileDev> td(n_tiles);
-    uint64_t pad = 0, outp = 0;
-    for (uint32_t i = 0; i < n_tiles; i++) {
-      const hrt_tile& t = tiles[i];
-      if (t.w == 0 || t.h == 0 || (uint64_t)t.x + t.w > p->width || (uint64_t)t.y + t.h > p->height)
-        throw HipError{HRT_ERR_INVALID_ARG, "tile outside the image"};
-      uint32_t bw = (t.w + 7) / 8, bh = (t.h + 7) / 8;
-      td[i] = G::TileDev{t.x, t.y, t.w, t.h, bw, (uint32_t)pad, (uint32_t)outp, 0};
-      pad += (uint64_t)bw * bh * 64; /* padded pixels (items: pad x n_chunks, chunk-major) */
-      outp += (uint64_t)t.w * t.h;
-    }
-    /* Many tiles (a rank's share of the 16-px grid: 4080 tiles at 2 GPUs): a claim's binary search over
-     * the tile table was a dozen dependent global loads.  When padding every tile to the largest one's
-     * item count costs at most 1/8 more (idle) items, tile = item / stride instead (share of 2 / 8 on C2:
-     * DESIGN.md section 6.1). */
-    uint32_t stride = 0;
-    if (n_tiles > 1) {
-      uint64_t mx = 0;
-      for (uint32_t i = 0; i < n_tiles; i++) mx = std::max<uint64_t>(mx, (uint64_t)((td[i].w + 7) / 8) * ((td[i].h + 7) / 8) * 64);
-      const char* ts = knob_env("HRT_TILE_STRIDE"); /* A/B knob: "0" keeps the binary search */
-      if (mx * n_tiles <= pad + pad / 8 && mx * n_tiles * n_chunks < 0xF0000000ull && !(ts && strcmp(ts, "0") == 0)) {
-        stride = (uint32_t)mx;
-        for (uint32_t i = 0; i < n_tiles; i++) td[i].pad_start = i * stride;
-        pad = mx * n_tiles;
-      }
-    }
-    /* work items and Item.slot (pixel x n_chunks + chunk < pad x n_chunks) are 32-bit */
-    /* headroom: waves claim blocks of CLAIM_BLOCK items past the end before they retire */
-    if (pad * n_chunks >= 0xF0000000ull) throw HipError{HRT_ERR_UNSUPPORTED, "more than 3.75G pixel x sample-chunk items in one call"};
-    hipStream_t stream = (hipStream_t)stream_;
-    DeviceGuard dg(s->device);
-    /* scratch slot: device [counter u32 | pad | stats 8 x u64 | pad to HDR | tiles], pinned host [stats | tiles] */
-    std::lock_guard<std::mutex> lock(*static_cast<std::mutex*>(s->slot_mutex));
-    /* an earlier launch whose walks the watchdog killed is reported by the first call that sees its
-     * copied-back error word (every launch copies it, with or without stats) */
-    for (auto& other : s->slots)
-      if (other.used && hipEventQuery((hipEvent_t)other.event) == hipSuccess) take_slot_error(other);
-    hrt_scene::Slot& sl = s->slots[s->next_slot++ % hrt_scene::N_SLOTS];
-    if (sl.used) {
-      hip_check(hipEventSynchronize((hipEvent_t)sl.event), "hipEventSynchronize(slot)");
-      take_slot_error(sl);
-    }
-    size_t tiles_bytes = n_tiles * sizeof(G::TileDev);
-    const size_t partial_bytes = n_chunks > 1 ? (size_t)n_chunks * outp * sizeof(float4) : 0;
-    auto grow = [&](hrt_scene::Slot& g, bool partial) {
-      if (tiles_bytes > g.tiles_cap) {
-        if (g.d_mem) hip_check(hipFree(g.d_mem), "hipFree(slot)");
-        if (g.h_tiles) hip_check(hipHostFree(g.h_tiles), "hipHostFree(slot)");
-        g.d_mem = g.h_tiles = nullptr;
-        g.tiles_cap = 0;
-        size_t cap = std::max<size_t>(tiles_bytes, 64 * sizeof(G::TileDev));
-        hip_check(hipMalloc(&g.d_mem, SLOT_HDR + cap), "hipMalloc(slot)");
-        hip_check(hipHostMalloc(&g.h_tiles, SLOT_HDR + cap, hipHostMallocDefault), "hipHostMalloc(slot)");
-        g.tiles_cap = cap;
-      }
-      if (partial && partial_bytes > g.partial_cap) {
-        if (g.d_partial) hip_check(hipFree(g.d_partial), "hipFree(partial)");
-        g.d_partial = nullptr;
-        g.partial_cap = 0;
-        hip_check(hipMalloc(&g.d_partial, partial_bytes), "hipMalloc(partial)");
-        g.partial_cap = partial_bytes;
-      }
-    };
-    /* slots never launched are grown with this one, so the next calls (e.g. a timed loop that keeps
-     * several launches in flight) do not allocate pinned and device memory between launches.  Their
-     * partial-sum buffers (a pixel's chunk sums: 1 GB for C2's 32 chunks) only when this call is
-     * asynchronous (no stats): a synchronous caller (hrt_render, a progressive batch with stats) never
-     * has a second launch in flight, and would otherwise hold N_SLOTS such buffers. */
-    const bool first_growth = tiles_bytes > sl.tiles_cap || partial_bytes > sl.partial_cap;
-    grow(sl, true);
-    if (first_growth)
-      for (auto& other : s->slots)
-        if (&other != &sl && !other.used) grow(other, stats == nullptr);
-    void* scratch = sl.d_mem;
-    memcpy((uint8_t*)sl.h_tiles + SLOT_HDR, td.data(), tiles_bytes);
-    hip_check(hipMemsetAsync(scratch, 0, SLOT_HDR, stream), "hipMemsetAsync");
-    hip_check(hipMemcpyAsync((uint8_t*)scratch + SLOT_HDR, (uint8_t*)sl.h_tiles + SLOT_HDR, tiles_bytes, hipMemcpyHostToDevice,
-                             stream), "hipMemcpyAsync(tiles)");
-    const Plan pl = plan(s, cam, p->flags);
-    KParams kp = scene_params(s, cam, p, pl);
-    kp.tiles = (const G::TileDev*)((uint8_t*)scratch + SLOT_HDR);
-    kp.n_tiles = n_tiles;
-    kp.total_work = (uint32_t)(pad * n_chunks);
-    kp.pad_px = (uint32_t)pad;
-    kp.head_items = (uint32_t)(pad * n_head);
-    kp.tile_stride = stride;
-    /* the sphere kernel claims blocks of items to the end: its passes are short, and per-lane claims
-     * made them wait on the contended counter (r02y: +12% on C2; per-lane claims for the last 0.26 /
-     * 1 / 4 M items measured +0.7 / -0.5 / -3% on C2 and -1 / -9 / -6% on a 1/8-frame share).  The
-     * segment kernels claim per lane: a segment iteration is long, claims are rare, and with few items
-     * per lane (Cornell 1024^2 x 128: 2) blocks unbalance the waves (-6%).
-     * HRT_CLAIM_FINE (A/B knob): claim the last that many items per lane, in every kernel but the sphere
-     * kernel, which decodes a claim once per 64-aligned block and so only ever claims whole blocks
-     * (kernel_common.h claim_blocks) */
-    const bool sphere_kernel = (!pl.full && !pl.fast && !pl.general) || pl.gwalk; /* block claims */
-    const char* cf = knob_env("HRT_CLAIM_FINE");
-    const uint64_t work = pad * n_chunks;
-    const uint64_t fine = cf ? strtoull(cf, nullptr, 10) : (sphere_kernel ? 0u : work);
-    kp.claim_fine = (uint32_t)(work > fine ? work - fine : 0);
-    kp.out = (float4*)d_rgba;
-    kp.counter = (uint32_t*)scratch;
-    kp.stats = (unsigned long long*)((uint8_t*)scratch + 8);
-    kp.chunk = chunk;
-    kp.n_chunks = n_chunks;
-    kp.chunk_head = n_head;
-    kp.chunk_first = first;
-    kp.n_out = (uint32_t)outp;
-    kp.partial = (float4*)sl.d_partial;
-    if (p->flags & HRT_RENDER_COUNT_WORK) launch_any<true>(s, pl, kp, stream);
-    else launch_any<false>(s, pl, kp, stream);
-    launch_knobs(s);
-    if (n_chunks > 1) {
-      uint32_t blocks = (uint32_t)std::min<uint64_t>((outp + 255) / 256, 4096);
-      hipLaunchKernelGGL(reduce_chunks, dim3(blocks), dim3(256), 0, stream, (const float4*)sl.d_partial,
-                         (float4*)d_rgba, (uint32_t)outp, n_chunks, spp);
-      hip_check(hipGetLastError(), "reduce_chunks launch");
-    }
-    /* the stats words and the watchdog's error word (h[12]) come back after EVERY launch, so a killed
-     * frame is reported even when the caller asked for no stats (take_slot_error) */
-    unsigned long long* h = (unsigned long long*)sl.h_tiles;
-    hip_check(hipMemcpyAsync(h, (uint8_t*)scratch + 8, 136, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(stats)");
-    hip_check(hipEventRecord((hipEvent_t)sl.event, stream), "hipEventRecord(slot)");
-    sl.used = true;
-    if (stats) {
-      hip_check(hipEventSynchronize((hipEvent_t)sl.event), "hipEventSynchronize(stats)");
-      take_slot_error(sl);
-      stats->segments = h[0];
-      stats->samples = h[1];
-      stats->pixels = h[2];
-      stats->node_visits = h[3];
-      stats->prim_tests = h[4];
-      stats->tex_evals = h[5];
-      stats->walk_slots = h[6];
-      stats->shade_slots = h[7];
-      stats->prim_slots = h[8];
-      for (int k = 0; k < 3; k++) stats->phase_cycles[k] = h[9 + k];
-      stats->park_slots = h[13];
-      stats->wait_slots = h[14];
-      stats->leaf_cycles = h[15];
-      stats->walk_steps = h[16];
-    }
+    SumsDest dst;
+    dst.d_rgba = d_rgba;
+    render_launch(s, cam, p, tiles, n_tiles, dst, stream_, stats, nullptr);
   });
 }
 
@@ -1214,6 +1433,231 @@ hrt_status hrt_debug_box_test(int32_t form, int32_t on_device, const float* boxe
                        tmin, tmax, dout);
     hip_check(hipGetLastError(), "box_test_kernel launch");
     hip_check(hipMemcpy(out, dout, n, hipMemcpyDeviceToHost), "hipMemcpy");
+  });
+}
+
+/* ---------------------------------------------------------------------------- sample accumulation */
+hrt_status hrt_accum_create(hrt_scene* s, uint32_t width, uint32_t height, const hrt_tile* tiles, uint32_t n_tiles,
+                            hrt_accum** out) {
+  return hguard([&] {
+    if (!s || !tiles || !out || n_tiles == 0) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_create: null argument or no tiles"};
+    *out = nullptr;
+    if (width < 2 || height < 2 || width > 65535 || height > 65535)
+      throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_create: 2 <= width, height <= 65535"};
+    uint64_t n_px = 0;
+    for (uint32_t i = 0; i < n_tiles; i++) {
+      const hrt_tile& t = tiles[i];
+      if (t.w == 0 || t.h == 0 || (uint64_t)t.x + t.w > width || (uint64_t)t.y + t.h > height)
+        throw HipError{HRT_ERR_INVALID_ARG, "tile outside the image"};
+      n_px += (uint64_t)t.w * t.h;
+    }
+    if (n_px >= (1ull << 32)) throw HipError{HRT_ERR_UNSUPPORTED, "more than 2^32 pixels in one accumulator"};
+    if (!s->committed || !s->d_blob) throw HipError{HRT_ERR_STATE, "scene not committed"};
+    DeviceGuard dg(s->device);
+    hrt_accum* a = new hrt_accum();
+    a->scene = s;
+    a->device = s->device;
+    a->width = width;
+    a->height = height;
+    a->tiles.assign(tiles, tiles + n_tiles);
+    a->n_px = (size_t)n_px;
+    try {
+      hip_check(hipMalloc((void**)&a->d_acc, a->n_px * sizeof(float4)), "hipMalloc(accumulator)");
+      hip_check(hipMemset(a->d_acc, 0, a->n_px * sizeof(float4)), "hipMemset(accumulator)");
+    } catch (...) {
+      if (a->d_acc) (void)hipFree(a->d_acc);
+      delete a;
+      throw;
+    }
+    *out = a;
+  });
+}
+
+void hrt_accum_destroy(hrt_accum* a) {
+  if (!a) return;
+  int prev = -1;
+  (void)hipGetDevice(&prev);
+  (void)hipSetDevice(a->device);
+  if (a->d_acc) (void)hipFree(a->d_acc); /* waits for the work that uses it */
+  if (prev >= 0) (void)hipSetDevice(prev);
+  delete a;
+}
+
+hrt_status hrt_accum_reset(hrt_accum* a, void* stream) {
+  return hguard([&] {
+    if (!a) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_reset: null accumulator"};
+    DeviceGuard dg(a->device);
+    hip_check(hipMemsetAsync(a->d_acc, 0, a->n_px * sizeof(float4), (hipStream_t)stream), "hipMemsetAsync(accumulator)");
+    a->ranges.clear();
+    a->has_identity = false;
+    a->invalid = false;
+  });
+}
+
+hrt_status hrt_accum_add(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, void* stream,
+                         hrt_render_stats* stats) {
+  return hguard([&] {
+    if (!a || !cam || !p) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_add: null argument"};
+    accum_add(a, cam, p, -1, nullptr, stream, stats);
+  });
+}
+
+hrt_status hrt_accum_add_resolve(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, int32_t format,
+                                 void* d_out, void* stream, hrt_render_stats* stats) {
+  return hguard([&] {
+    if (!a || !cam || !p || !d_out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_add_resolve: null argument"};
+    accum_format(format);
+    accum_add(a, cam, p, format, d_out, stream, stats);
+  });
+}
+
+hrt_status hrt_accum_samples(const hrt_accum* a, uint64_t* samples) {
+  return hguard([&] {
+    if (!a || !samples) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_samples: null argument"};
+    *samples = ranges_total(a->ranges);
+  });
+}
+
+hrt_status hrt_accum_resolve(hrt_accum* a, int32_t format, void* d_out, void* stream) {
+  return hguard([&] {
+    if (!a || !d_out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_resolve: null argument"};
+    accum_format(format);
+    accum_usable(a);
+    if (a->ranges.empty()) throw HipError{HRT_ERR_STATE, "the accumulator holds no samples"};
+    DeviceGuard dg(a->device);
+    launch_resolve(a, format, d_out, (hipStream_t)stream);
+  });
+}
+
+hrt_status hrt_accum_resolve_host(hrt_accum* a, int32_t format, void* out) {
+  OutBuf buf{nullptr, 0};
+  const hrt_status st = hguard([&] {
+    if (!a || !out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_resolve_host: null argument"};
+    accum_format(format);
+    accum_usable(a);
+    if (a->ranges.empty()) throw HipError{HRT_ERR_STATE, "the accumulator holds no samples"};
+    DeviceGuard dg(a->device);
+    const size_t bytes = a->n_px * (format == HRT_ACCUM_F32 ? 16u : 4u);
+    buf = out_pool_take(a->scene, a->n_px * 16 + 16);
+    hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize"); /* passes the caller queued on any stream */
+    launch_resolve(a, format, buf.ptr, nullptr);
+    hip_check(hipMemcpy(out, buf.ptr, bytes, hipMemcpyDeviceToHost), "hipMemcpy(resolve)");
+  });
+  if (a && buf.ptr) out_pool_give(a->scene, buf);
+  return st;
+}
+
+hrt_status hrt_accum_merge(hrt_accum* dst, const hrt_accum* src, void* stream) {
+  return hguard([&] {
+    if (!dst || !src || dst == src) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_merge: null argument, or an accumulator into itself"};
+    accum_usable(dst);
+    accum_usable(src);
+    if (dst->device != src->device || dst->width != src->width || dst->height != src->height ||
+        dst->tiles.size() != src->tiles.size() ||
+        memcmp(dst->tiles.data(), src->tiles.data(), dst->tiles.size() * sizeof(hrt_tile)) != 0)
+      throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_merge: the accumulators differ in device, image size or tiles"};
+    if (src->ranges.empty()) return;
+    check_identity(dst, src->identity);
+    for (const SampleRange& r : src->ranges) check_range(dst->ranges, r);
+    DeviceGuard dg(dst->device);
+    hipLaunchKernelGGL(accum_merge, dim3(stream_blocks(dst->n_px)), dim3(256), 0, (hipStream_t)stream, dst->d_acc,
+                       (const float4*)src->d_acc, dst->n_px);
+    hip_check(hipGetLastError(), "accum_merge launch");
+    dst->identity = src->identity;
+    dst->has_identity = true;
+    for (const SampleRange& r : src->ranges) ranges_insert(dst->ranges, r);
+  });
+}
+
+hrt_status hrt_accum_download(hrt_accum* a, float* sums, uint32_t* ranges, uint32_t cap, uint32_t* n_ranges) {
+  return hguard([&] {
+    if (!a || !n_ranges) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_download: null argument"};
+    accum_usable(a);
+    *n_ranges = (uint32_t)a->ranges.size();
+    if (!sums || cap < a->ranges.size()) return;
+    if (!ranges && !a->ranges.empty()) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_download: null ranges"};
+    for (size_t i = 0; i < a->ranges.size(); i++) {
+      ranges[2 * i] = (uint32_t)a->ranges[i].begin;
+      ranges[2 * i + 1] = (uint32_t)a->ranges[i].end; /* 2^32 wraps to 0 */
+    }
+    DeviceGuard dg(a->device);
+    hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    hip_check(hipMemcpy(sums, a->d_acc, a->n_px * sizeof(float4), hipMemcpyDeviceToHost), "hipMemcpy(download)");
+  });
+}
+
+hrt_status hrt_accum_upload(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, const float* sums,
+                            const uint32_t* ranges, uint32_t n_ranges) {
+  return hguard([&] {
+    if (!a || !cam || !p || !sums || (!ranges && n_ranges)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_upload: null argument"};
+    accum_usable(a);
+    const FrameIdentity id = frame_identity(cam, p);
+    check_identity(a, id);
+    /* the ranges must be addable one after the other: checked on a copy, so an error changes nothing */
+    std::vector<SampleRange> held = a->ranges;
+    for (uint32_t i = 0; i < n_ranges; i++) {
+      const uint64_t b = ranges[2 * i], e = ranges[2 * i + 1] == 0 ? (1ull << 32) : ranges[2 * i + 1];
+      const SampleRange r{b, e};
+      check_range(held, r);
+      ranges_insert(held, r);
+    }
+    if (n_ranges == 0) return;
+    DeviceGuard dg(a->device);
+    hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    if (a->ranges.empty()) { /* no samples: the sums as they are */
+      hip_check(hipMemcpy(a->d_acc, sums, a->n_px * sizeof(float4), hipMemcpyHostToDevice), "hipMemcpy(upload)");
+    } else {
+      DevBuf<float4> tmp(a->n_px * sizeof(float4));
+      hip_check(hipMemcpy(tmp.p, sums, a->n_px * sizeof(float4), hipMemcpyHostToDevice), "hipMemcpy(upload)");
+      hipLaunchKernelGGL(accum_merge, dim3(stream_blocks(a->n_px)), dim3(256), 0, nullptr, a->d_acc, (const float4*)tmp.p, a->n_px);
+      hip_check(hipGetLastError(), "accum_merge launch");
+      hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    }
+    a->identity = id;
+    a->has_identity = true;
+    a->ranges = held;
+  });
+}
+
+hrt_status hrt_debug_accumulate(int32_t on_device, const float* partial, uint32_t n_chunks, uint32_t n, float* acc_inout,
+                                uint64_t samples, int32_t format, void* out) {
+  return hguard([&] {
+    if (!partial || !acc_inout || n_chunks == 0 || format < -1 || format > HRT_ACCUM_RGBA8 ||
+        (format >= 0 && (!out || samples == 0 || samples > (1ull << 32))))
+      throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_accumulate: bad argument"};
+    if (n == 0) return;
+    const float scale = format >= 0 ? accum::resolve_scale(samples) : 0.0f;
+    const size_t out_bytes = format < 0 ? 0 : (size_t)n * (format == HRT_ACCUM_F32 ? 16u : 4u);
+    if (!on_device) {
+      const float4* hp = reinterpret_cast<const float4*>(partial);
+      float4* ha = reinterpret_cast<float4*>(acc_inout);
+      for (size_t i = 0; i < n; i++) {
+        if (format == HRT_ACCUM_F32) accumulate_pixel<HRT_ACCUM_F32>(hp, ha, n, n_chunks, scale, out, i);
+        else if (format == HRT_ACCUM_RGBA8) accumulate_pixel<HRT_ACCUM_RGBA8>(hp, ha, n, n_chunks, scale, out, i);
+        else accumulate_pixel<-1>(hp, ha, n, n_chunks, scale, out, i);
+      }
+      return;
+    }
+    /* the real kernels on the calling thread's current device: the fused accumulate + resolve, and the separate
+     * resolve of the same sums, which must agree */
+    const size_t p_bytes = (size_t)n_chunks * n * sizeof(float4), a_bytes = (size_t)n * sizeof(float4);
+    DevBuf<float4> d_partial(p_bytes), d_acc(a_bytes);
+    DevBuf<uint8_t> d_out(out_bytes + 16), d_out2(out_bytes + 16);
+    hip_check(hipMemcpy(d_partial.p, partial, p_bytes, hipMemcpyHostToDevice), "hipMemcpy");
+    hip_check(hipMemcpy(d_acc.p, acc_inout, a_bytes, hipMemcpyHostToDevice), "hipMemcpy");
+    launch_accumulate(format, d_partial.p, d_acc.p, n, n_chunks, scale, d_out.p, nullptr);
+    hip_check(hipMemcpy(acc_inout, d_acc.p, a_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+    if (format < 0) return;
+    if (format == HRT_ACCUM_F32)
+      hipLaunchKernelGGL((accum_resolve<HRT_ACCUM_F32>), dim3(stream_blocks(n)), dim3(256), 0, nullptr, (const float4*)d_acc.p, (size_t)n, scale, (void*)d_out2.p);
+    else
+      hipLaunchKernelGGL((accum_resolve<HRT_ACCUM_RGBA8>), dim3(stream_blocks(n)), dim3(256), 0, nullptr, (const float4*)d_acc.p, (size_t)n, scale, (void*)d_out2.p);
+    hip_check(hipGetLastError(), "accum_resolve launch");
+    std::vector<uint8_t> second(out_bytes);
+    hip_check(hipMemcpy(out, d_out.p, out_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+    hip_check(hipMemcpy(second.data(), d_out2.p, out_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+    if (memcmp(out, second.data(), out_bytes) != 0)
+      throw HipError{HRT_ERR_STATE, "hrt_debug_accumulate: accumulate_chunks' fused resolve and accum_resolve differ"};
   });
 }
 

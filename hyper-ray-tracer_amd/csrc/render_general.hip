@@ -297,7 +297,7 @@ void render_gwalk_kernel(KParams P) {
         node = G::NONE;
         sample_done = true;
         const Vec3 c = v3(0.0f, 0.0f, 0.0f) + ps.rad; /* the chunk's sum, as the general case forms it */
-        if (P.n_chunks == 1)
+        if (P.direct_out == 1)
           P.out[*slot_lds] = make_float4(sqrtf(c.x * scale), sqrtf(c.y * scale), sqrtf(c.z * scale), 1.0f);
         else
           P.partial[*slot_lds] = make_float4(c.x, c.y, c.z, 0.0f);
@@ -309,7 +309,7 @@ void render_gwalk_kernel(KParams P) {
         sum = sum + ps.rad; /* application.rs:448: samples of a chunk summed in order */
         sample_done = true;
         if (++it.sample == it.sample_end) {
-          if (P.n_chunks == 1)
+          if (P.direct_out == 1)
             P.out[*slot_lds] = make_float4(sqrtf(sum.x * scale), sqrtf(sum.y * scale), sqrtf(sum.z * scale), 1.0f);
           else
             P.partial[*slot_lds] = make_float4(sum.x, sum.y, sum.z, 0.0f);

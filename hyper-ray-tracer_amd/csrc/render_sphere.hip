@@ -288,7 +288,7 @@ void render_basic_kernel(KParams P) {
         if constexpr (!WS) sum = sum + ps.rad; /* shade_walk added a miss's radiance already */
         sample_done = true;
         if (++it.sample == it.sample_end) {
-          if (P.n_chunks == 1) /* sqrt(sum / spp), alpha 1 (:451-456) */
+          if (P.direct_out == 1) /* sqrt(sum / spp), alpha 1 (:451-456) */
             P.out[*slot_lds] = make_float4(sqrtf(sum.x * scale), sqrtf(sum.y * scale), sqrtf(sum.z * scale), 1.0f);
           else
             P.partial[*slot_lds] = make_float4(sum.x, sum.y, sum.z, 0.0f);

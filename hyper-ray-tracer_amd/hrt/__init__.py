@@ -150,7 +150,10 @@ class SceneOptions(ctypes.Structure):
 
 # Diagnostics an older build may lack; only tolerated when HRT_LIB points at another build (A/B runs)
 OPTIONAL = {"hrt_abi_version", "hrt_last_launch", "hrt_debug_box_test", "hrt_scene_set_options", "hrt_scene_get_options",
-            "hrt_debug_sample_chunks", "hrt_scene_set_view"}
+            "hrt_debug_sample_chunks", "hrt_scene_set_view",
+            "hrt_accum_create", "hrt_accum_destroy", "hrt_accum_reset", "hrt_accum_add", "hrt_accum_add_resolve",
+            "hrt_accum_samples", "hrt_accum_resolve", "hrt_accum_resolve_host", "hrt_accum_merge", "hrt_accum_download",
+            "hrt_accum_upload", "hrt_debug_accumulate"}
 HRT_LIB_OVERRIDE = bool(os.environ.get("HRT_LIB"))
 
 # Every entry point of include/hrt/hrt.h (tests/test_abi.py checks the header against this list).
@@ -165,6 +168,9 @@ EXPORTS = [
     "hrt_debug_device_math", "hrt_debug_trace_path", "hrt_debug_scene_blob", "hrt_image_write", "hrt_render_progressive", "hrt_debug_prim_record",
     "hrt_scene_synchronize", "hrt_debug_poke_blob", "hrt_scene_set_options", "hrt_scene_get_options",
     "hrt_debug_sample_chunks", "hrt_scene_set_view",
+    "hrt_accum_create", "hrt_accum_destroy", "hrt_accum_reset", "hrt_accum_add", "hrt_accum_add_resolve", "hrt_accum_samples",
+    "hrt_accum_resolve", "hrt_accum_resolve_host", "hrt_accum_merge", "hrt_accum_download", "hrt_accum_upload",
+    "hrt_debug_accumulate",
 ]
 
 ABI_VERSION = 6  # include/hrt/hrt.h HRT_ABI_VERSION: the struct layouts below
@@ -243,6 +249,19 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "hrt_scene_get_options": (S, [vp, ctypes.POINTER(SceneOptions)]),
         "hrt_scene_set_view": (S, [vp, ctypes.POINTER(Camera)]),
         "hrt_debug_sample_chunks": (S, [vp, ctypes.POINTER(RenderParams), _U32P]),
+        "hrt_accum_create": (S, [vp, u32, u32, vp, u32, ctypes.POINTER(vp)]),
+        "hrt_accum_destroy": (None, [vp]),
+        "hrt_accum_reset": (S, [vp, vp]),
+        "hrt_accum_add": (S, [vp, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams), vp, ctypes.POINTER(RenderStats)]),
+        "hrt_accum_add_resolve": (S, [vp, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams), i32, vp, vp,
+                                      ctypes.POINTER(RenderStats)]),
+        "hrt_accum_samples": (S, [vp, ctypes.POINTER(u64)]),
+        "hrt_accum_resolve": (S, [vp, i32, vp, vp]),
+        "hrt_accum_resolve_host": (S, [vp, i32, vp]),
+        "hrt_accum_merge": (S, [vp, vp, vp]),
+        "hrt_accum_download": (S, [vp, vp, vp, u32, _U32P]),
+        "hrt_accum_upload": (S, [vp, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams), vp, vp, u32]),
+        "hrt_debug_accumulate": (S, [i32, vp, u32, u32, vp, u64, i32, vp]),
     }
     for name, (res, args) in sig.items():
         if name in OPTIONAL and HRT_LIB_OVERRIDE and not hasattr(L, name):
@@ -276,6 +295,7 @@ class Scene:
         _check(L.hrt_scene_create(ctypes.byref(h)))
         self.h = h
         self.info: Optional[PresetInfo] = None
+        self.device = -1
         self._keep: list = []
 
     def close(self):
@@ -398,6 +418,7 @@ class Scene:
 
     def commit(self, device: int = -1):
         _check(load().hrt_scene_commit(self.h, device))
+        self.device = device  # -1: the device that was current at the commit
 
     def synchronize(self):
         """Wait for every render launched on this scene; raises HrtError(ERR_STATE) if one of them
@@ -511,6 +532,114 @@ def render_tiles_device(scene: Scene, cam: Camera, p: RenderParams, tiles, d_out
     _check(load().hrt_render_tiles_device(scene.h, ctypes.byref(cam), ctypes.byref(p), ctypes.cast(arr, ctypes.c_void_p), len(tiles),
                                           ctypes.c_void_p(d_out_ptr), ctypes.c_void_p(stream_ptr), ctypes.byref(st) if want_stats else None))
     return st if want_stats else None
+
+
+ACCUM_F32, ACCUM_RGBA8 = 0, 1
+_ACCUM_FORMATS = {"f32": ACCUM_F32, "rgba8": ACCUM_RGBA8}
+
+
+class Accumulator:
+    """hrt_accum: device-resident raw per-pixel sums of a tile set (the whole frame when `tiles` is None).  Passes
+    add sample ranges (`add` with params.sample_offset / params.samples), and `resolve` gives the frame of the
+    samples held so far.  The frame's bits depend on the pass schedule alone (include/hrt/hrt.h)."""
+
+    def __init__(self, scene: Scene, width: int, height: int, tiles=None):
+        self.scene, self.width, self.height = scene, int(width), int(height)  # the scene must outlive the accumulator
+        self.tiles = [tuple(int(v) for v in t) for t in tiles] if tiles is not None else [(0, 0, self.width, self.height)]
+        self.n_pixels = sum(t[2] * t[3] for t in self.tiles)
+        self.h = ctypes.c_void_p()
+        arr = (Tile * max(1, len(self.tiles)))(*[Tile(*t) for t in self.tiles])
+        _check(load().hrt_accum_create(scene.h, self.width, self.height, ctypes.cast(arr, ctypes.c_void_p), len(self.tiles),
+                                       ctypes.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            load().hrt_accum_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _shaped(self, flat: np.ndarray) -> np.ndarray:
+        """(h, w, 4) for one tile (as hrt.render), else the packed (n_pixels, 4)."""
+        if len(self.tiles) == 1:
+            return flat.reshape(self.tiles[0][3], self.tiles[0][2], 4)
+        return flat.reshape(self.n_pixels, 4)
+
+    def add(self, cam: Camera, p: RenderParams, stats: bool = False, preview=None):
+        """Render samples [p.sample_offset, p.sample_offset + p.samples) of every pixel and add them.  preview
+        ("f32" / "rgba8", or True for "f32"): also return the frame after this pass, resolved by the kernel that adds
+        the pass (hrt_accum_add_resolve).  Returns None, RenderStats, the preview, or (preview, RenderStats)."""
+        st = RenderStats()
+        sp = ctypes.byref(st) if stats else None
+        if preview is None or preview is False:
+            _check(load().hrt_accum_add(self.h, ctypes.byref(cam), ctypes.byref(p), None, sp))
+            return st if stats else None
+        import torch
+
+        fmt = "f32" if preview is True else preview
+        dev = torch.device("cuda", self.scene.device if self.scene.device >= 0 else torch.cuda.current_device())
+        buf = torch.empty(self.n_pixels * 4, dtype=torch.float32 if fmt == "f32" else torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        _check(load().hrt_accum_add_resolve(self.h, ctypes.byref(cam), ctypes.byref(p), _ACCUM_FORMATS[fmt],
+                                            ctypes.c_void_p(buf.data_ptr()), ctypes.c_void_p(stream.cuda_stream), sp))
+        stream.synchronize()
+        img = self._shaped(buf.cpu().numpy())
+        return (img, st) if stats else img
+
+    @property
+    def samples(self) -> int:
+        n = ctypes.c_uint64()
+        _check(load().hrt_accum_samples(self.h, ctypes.byref(n)))
+        return n.value
+
+    def resolve(self, fmt: str = "f32") -> np.ndarray:
+        """The frame of the samples held: float32 sqrt(sum / samples) with alpha 1 shaped like hrt.render's result,
+        or uint8 (the PPM rule, alpha 255); several tiles: packed (n_pixels, 4)."""
+        out = np.zeros(self.n_pixels * 4, np.float32 if fmt == "f32" else np.uint8)
+        _check(load().hrt_accum_resolve_host(self.h, _ACCUM_FORMATS[fmt], out.ctypes.data))
+        return self._shaped(out)
+
+    def merge(self, other: "Accumulator"):
+        """self += other (same scene device, tiles and frame identity; disjoint sample ranges)."""
+        _check(load().hrt_accum_merge(self.h, other.h, None))
+
+    def download(self):
+        """(sums, ranges): the raw sums as (n_pixels, 4) float32 (w = 0) and the [(begin, end), ...] held."""
+        n = ctypes.c_uint32()
+        _check(load().hrt_accum_download(self.h, None, None, 0, ctypes.byref(n)))
+        sums = np.zeros((self.n_pixels, 4), np.float32)
+        rng = np.zeros(2 * max(1, n.value), np.uint32)
+        _check(load().hrt_accum_download(self.h, sums.ctypes.data, rng.ctypes.data, n.value, ctypes.byref(n)))
+        return sums, [(int(rng[2 * i]), int(rng[2 * i + 1]) or 1 << 32) for i in range(n.value)]
+
+    def upload(self, cam: Camera, p: RenderParams, sums: np.ndarray, ranges):
+        """Put downloaded sums and their ranges into this accumulator under the frame identity of (cam, p)."""
+        s = np.ascontiguousarray(sums, np.float32)
+        if s.size != self.n_pixels * 4:
+            raise ValueError("sums must hold n_pixels x 4 float32")
+        rng = np.array([[b, e & 0xFFFFFFFF] for b, e in ranges], np.uint32).reshape(-1)
+        _check(load().hrt_accum_upload(self.h, ctypes.byref(cam), ctypes.byref(p), s.ctypes.data,
+                                       rng.ctypes.data if rng.size else None, len(ranges)))
+
+    def reset(self):
+        _check(load().hrt_accum_reset(self.h, None))
+
+
+def debug_accumulate(partial: np.ndarray, acc: np.ndarray, samples: int = 0, fmt: Optional[str] = None, on_device: bool = False):
+    """hrt_debug_accumulate: csrc/accum.h on the host, or the real kernels on the current device.  partial:
+    (n_chunks, n, 4) float32 chunk sums of one pass, acc: (n, 4) float32 sums before it.  Returns (acc after the pass,
+    the frame of `samples` samples in `fmt`: (n, 4) float32 / uint8, or None without fmt)."""
+    pa = np.ascontiguousarray(partial, np.float32)
+    n_chunks, n = pa.shape[0], pa.shape[1]
+    a = np.array(acc, np.float32).reshape(n, 4).copy()
+    out = None if fmt is None else np.zeros((n, 4), np.float32 if fmt == "f32" else np.uint8)
+    _check(load().hrt_debug_accumulate(1 if on_device else 0, pa.ctypes.data, n_chunks, n, a.ctypes.data, int(samples),
+                                       -1 if fmt is None else _ACCUM_FORMATS[fmt], None if out is None else out.ctypes.data))
+    return a, out
 
 
 def last_launch() -> Optional[dict]:

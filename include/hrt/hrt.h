@@ -299,6 +299,70 @@ hrt_status hrt_render(hrt_scene* s, const hrt_camera* cam, const hrt_render_para
 hrt_status hrt_tile_grid(uint32_t width, uint32_t height, uint32_t tile_size, uint32_t rank,
                          uint32_t world, hrt_tile* tiles, uint32_t cap, uint32_t* n);
 
+/* ---- progressive sample accumulation ---- */
+/* A device-resident accumulator of raw per-pixel radiance sums (RGB f32, 16 B per pixel) for a tile set of one
+ * frame.  Renders add sample ranges of every pixel into it, and it can be resolved to a displayable frame at any
+ * time: refinement pass by pass (a whole frame at 16 spp after a few milliseconds, then more samples), a frame
+ * whose samples are split across devices or jobs (download, upload, merge), checkpoint and resume.
+ *
+ * THE BIT CONTRACT (next to hrt_scene_options.chunk_*, which fixes the bits of one render):
+ *   - one hrt_accum_add computes the pass sum of a pixel exactly as hrt_render does for those params: the chunk
+ *     schedule of p->samples (hrt_debug_sample_chunks), chunk sums added in chunk order starting from chunk 0's;
+ *   - the accumulator then does acc = acc + pass_sum per channel in f32; hrt_accum_merge does dst = dst + src;
+ *   - hrt_accum_resolve gives sqrtf(acc * (1.0f / (float)samples)), the render calls' expression.
+ * So one add into an empty accumulator followed by a resolve to HRT_ACCUM_F32 equals hrt_render_tiles_device
+ * with the same params bit for bit, and a frame of several passes is a function of the PASS SCHEDULE alone (which
+ * sample ranges were added or merged, in which order): it never depends on the tile split or the device count.
+ *
+ * Frame identity: the first add or upload fixes it: the camera's bytes and the params' width, height, max_depth,
+ * flags, t_min, background and seed (everything but samples and sample_offset).  A later add, upload or merge with
+ * another identity is HRT_ERR_INVALID_ARG; hrt_accum_reset clears it.
+ * Sample ranges: the accumulator keeps the sorted, disjoint, coalesced [begin, end) ranges it holds.  An add,
+ * upload or merge that overlaps one of them (a sample counted twice biases the image silently) or whose end
+ * exceeds 2^32 is HRT_ERR_INVALID_ARG and changes nothing.
+ * Streams: as hrt_render_tiles_device: work is asynchronous on `stream`, the caller orders its uses of an
+ * accumulator as it does those of d_rgba, and the host bookkeeping (ranges, identity) is updated at call time.
+ * hrt_accum_resolve_host, hrt_accum_download and hrt_accum_upload wait for the device.  An add that reports
+ * HRT_ERR_STATE with stats (walk watchdog) leaves the accumulator invalid: only reset and destroy then succeed.
+ * The accumulator must be destroyed before its scene, and calls on ONE accumulator must not run concurrently
+ * (different accumulators of a scene may be used from different threads, as the render calls may). */
+typedef struct hrt_accum hrt_accum;
+enum {
+  HRT_ACCUM_F32 = 0,  /* RGBA f32: sqrt(sum * (1 / samples)), alpha 1: the render calls' rule */
+  HRT_ACCUM_RGBA8 = 1 /* 4 x u8: hrt_image_write's PPM rule per channel on the F32 value, alpha 255 */
+};
+/* Sums for `tiles` of a width x height image, packed as hrt_render_tiles_device packs its output; zeroed, no
+ * samples.  The scene must be committed (HRT_ERR_STATE); the accumulator lives on the scene's device. */
+hrt_status hrt_accum_create(hrt_scene* s, uint32_t width, uint32_t height, const hrt_tile* tiles, uint32_t n_tiles,
+                            hrt_accum** out);
+void hrt_accum_destroy(hrt_accum* a);
+hrt_status hrt_accum_reset(hrt_accum* a, void* stream);
+/* Render samples [p->sample_offset, p->sample_offset + p->samples) of every pixel and add them.  stats: the
+ * counters of this pass alone (synchronises, as hrt_render_tiles_device). */
+hrt_status hrt_accum_add(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, void* stream,
+                         hrt_render_stats* stats);
+/* hrt_accum_add, and the frame after this pass resolved to d_out by the same kernel that adds the pass (a
+ * preview after every pass costs no extra kernel). */
+hrt_status hrt_accum_add_resolve(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, int32_t format,
+                                 void* d_out, void* stream, hrt_render_stats* stats);
+hrt_status hrt_accum_samples(const hrt_accum* a, uint64_t* samples);
+/* d_out: device memory, n_pixels x 16 B (F32) or x 4 B (RGBA8), packed as the tiles are.  HRT_ERR_STATE with no
+ * samples. */
+hrt_status hrt_accum_resolve(hrt_accum* a, int32_t format, void* d_out, void* stream);
+/* The same into caller-owned host memory; synchronous. */
+hrt_status hrt_accum_resolve_host(hrt_accum* a, int32_t format, void* out);
+/* dst += src (same device, same tile set, same frame identity, disjoint sample ranges). */
+hrt_status hrt_accum_merge(hrt_accum* dst, const hrt_accum* src, void* stream);
+/* Checkpoint / transport: the raw sums (n_pixels x 4 f32, w = 0) and the sample ranges as [begin, end) pairs of
+ * u32 (an end of 2^32 is stored as 0).  *n_ranges = the number of ranges; sums and ranges are written only when
+ * cap >= that number (sums may be NULL to ask for the count).  Upload puts them into the accumulator under the
+ * identity of (cam, p), whose samples and sample_offset are ignored: an accumulator without samples takes the
+ * sums as they are (so download + upload reproduces an accumulator bit for bit), one with samples adds them as
+ * a merge does. */
+hrt_status hrt_accum_download(hrt_accum* a, float* sums, uint32_t* ranges, uint32_t cap, uint32_t* n_ranges);
+hrt_status hrt_accum_upload(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, const float* sums,
+                            const uint32_t* ranges, uint32_t n_ranges);
+
 /* ---- diagnostics ---- */
 /* Device occupancy / layout facts of the committed scene (for DESIGN/bench). */
 typedef struct hrt_scene_info {
@@ -398,6 +462,13 @@ hrt_status hrt_debug_device_math(int32_t op, const float* x, const float* y, flo
  * device's culling decisions to the host's bit for bit. */
 hrt_status hrt_debug_box_test(int32_t form, int32_t on_device, const float* boxes, uint32_t n_boxes, const float* rays,
                               uint32_t n_rays, float tmin, float tmax, uint8_t* out);
+/* The accumulator's arithmetic (csrc/accum.h) on the DEVICE through the real kernels (on_device = 1: the calling
+ * thread's current HIP device) or with the same code compiled for the host (0): partial is one pass's chunk sums
+ * [n_chunks][n] x 4 f32, acc_inout the n x 4 f32 sums before and after the pass (w = 0), out the frame of
+ * `samples` samples in an HRT_ACCUM_* format after it (format -1: no resolve, out unused).  Used by the tests
+ * that check the arithmetic without a GPU and hold the device to the host bit for bit. */
+hrt_status hrt_debug_accumulate(int32_t on_device, const float* partial, uint32_t n_chunks, uint32_t n, float* acc_inout,
+                                uint64_t samples, int32_t format, void* out);
 
 #ifdef __cplusplus
 }
