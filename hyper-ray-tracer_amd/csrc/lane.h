@@ -97,6 +97,10 @@ struct KParams {
   uint32_t walk_c16;   /* 16-B node parts (layout.h WALK_C16): walk_end is then the node count */
   uint32_t walk_pbase; /* walk_c16: byte offset of the payloads */
   uint32_t n_chunks;   /* chunks per pixel (host side and the lane simulator; the kernels read direct_out) */
+  /* the camera segment's leaf lists (primary_list.h): one 16-B record per frame-aligned 8x8 pixel cell, cell
+   * (px >> 3, py >> 3) at [(py >> 3) * cells_x + (px >> 3)]; null: every ray walks the stream */
+  const uint4* prim_lists;
+  uint32_t cells_x;
 };
 
 /* Sample-chunk size: spp <= cmin keeps one work item per pixel (the reference's sequential sum), larger
@@ -1774,6 +1778,19 @@ HRT_LANE_FI void walk_prim(const KParams& P, const WalkSrc& src, uint32_t& i, co
   const uint32_t leaf = pend_payload<C16>(P, i); /* the leaf's payload */
   i = walk_successor<MEM>(src, leaf); /* the walk goes on at the leaf's pre-order successor */
   walk_leaf_test<COUNT, MEM>(P, src, leaf, r, closest, winner, cn);
+}
+
+/* One entry of a camera segment's leaf list (primary_list.h): an ordinary walk_box step on the listed leaf's node
+ * part at byte offset `off`, with the lane's current closest.  True when the leaf's inflated box passes: `leaf`
+ * is then its payload, for walk_leaf_test.  A list holds, in leaf order, every leaf whose step can pass for the
+ * ray, so the steps and tests of a list are those of the stream walk's leaves. */
+template <bool COUNT, int MEM, bool FMA = HRT_BOX_FMA != 0>
+HRT_LANE_FI bool list_step(const WalkSrc& src, uint32_t off, const TRay& r, float tmin, float closest, Counts& cn,
+                           uint32_t& leaf) {
+  uint32_t i = off;
+  walk_box<COUNT, MEM, FMA, false>(src, i, r, tmin, closest, cn);
+  leaf = i - G::WALK_PEND;
+  return walk_pending(i);
 }
 
 /* A one-node program (layout.h GL_ONE): trace_ray's body for a K_BOX_PRIM or K_PRIM node -- the node's

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "accum.h"
+#include "primary_list.h"
 #include "kernel_common.h"
 
 using namespace hrt;
@@ -858,6 +859,7 @@ void device_release(hrt_scene* s) {
     }
     if (sl.d_mem) (void)hipFree(sl.d_mem);
     if (sl.d_partial) (void)hipFree(sl.d_partial);
+    if (sl.d_lists) (void)hipFree(sl.d_lists);
     if (sl.h_tiles) (void)hipHostFree(sl.h_tiles);
     sl = hrt_scene::Slot();
   }
@@ -916,6 +918,58 @@ void launch_accumulate(int format, const float4* partial, float4* acc, size_t n,
   if (format == HRT_ACCUM_F32) launch_accumulate<HRT_ACCUM_F32>(partial, acc, n, n_chunks, scale, out, stream);
   else if (format == HRT_ACCUM_RGBA8) launch_accumulate<HRT_ACCUM_RGBA8>(partial, acc, n, n_chunks, scale, out, stream);
   else launch_accumulate<-1>(partial, acc, n, n_chunks, 0.0f, nullptr, stream);
+}
+
+/* The camera segment's leaf lists (primary_list.h), built on the launch's stream ahead of the megakernel: one
+ * thread per 8x8 pixel cell of the frame runs the builder over the stream's leaves.  A workgroup stages the
+ * stream in LDS first (it is one the sphere kernel stages whole), so the builder's walk through the links reads
+ * LDS, not one dependent global load per node. */
+constexpr int LISTS_BLOCK = 256;
+__global__ __launch_bounds__(LISTS_BLOCK) void build_primary_lists(KParams P, uint32_t cap, uint32_t n_cells, uint4* out) {
+  extern __shared__ float4 lds_stream[];
+  const float4* g = reinterpret_cast<const float4*>(P.walk);
+  for (uint32_t k = threadIdx.x; k < P.walk_bytes / 16u; k += blockDim.x) lds_stream[k] = g[k];
+  __syncthreads();
+  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n_cells) return;
+  KParams Q = P;
+  Q.walk = reinterpret_cast<const uint8_t*>(lds_stream);
+  plist::Record rec;
+  plist::build_cell(Q, c % P.cells_x, c / P.cells_x, cap, rec);
+  out[c] = *reinterpret_cast<const uint4*>(&rec);
+}
+
+/* The capacity of the leaf lists a launch builds, 0 for none.  Lists are built for the sphere kernel's plain
+ * instantiation alone: a sphere stream staged whole in LDS with 32-B node parts under exact culling (not HEAVY,
+ * hybrid, split, 16-B parts or the packet walk), short enough for the records' 16-bit entries.
+ * HRT_PRIMARY_LISTS (A/B knob): "0" builds none, 1..8 is the capacity (cells with more leaves walk the stream). */
+uint32_t primary_list_cap(const hrt_scene* s, const Plan& pl) {
+  if (pl.full || pl.fast || pl.general || pl.gwalk || pl.heavy || pl.sphere_packet || !pl.lds || pl.cull != G::CULL_EXACT)
+    return 0;
+  if (s->w_general || s->w_hot || s->w_c16 || s->w_half != 16u || s->w_end == 0 || s->w_end > plist::PL_MAX_WALK_BYTES) return 0;
+  const char* e = knob_env("HRT_PRIMARY_LISTS");
+  if (!e) return plist::PL_CAP;
+  const long x = strtol(e, nullptr, 10);
+  return x >= 1 && x <= (long)plist::PL_CAP ? (uint32_t)x : 0u;
+}
+
+void launch_primary_lists(const hrt_scene* s, const KParams& kp, uint32_t cap, uint32_t n_cells, void* d_lists, hipStream_t stream) {
+  static std::mutex mu;
+  static std::vector<std::pair<int, size_t>> sized; /* (device, LDS bytes) the kernel's limit was raised for */
+  const size_t smem = kp.walk_bytes;
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    bool have = false;
+    for (const auto& d : sized) have = have || (d.first == s->device && d.second >= smem);
+    if (!have) {
+      hip_check(hipFuncSetAttribute((const void*)build_primary_lists, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem),
+                "hipFuncSetAttribute(lists)");
+      sized.emplace_back(s->device, smem);
+    }
+  }
+  hipLaunchKernelGGL(build_primary_lists, dim3((n_cells + LISTS_BLOCK - 1) / LISTS_BLOCK), dim3(LISTS_BLOCK), smem, stream, kp,
+                     cap, n_cells, (uint4*)d_lists);
+  hip_check(hipGetLastError(), "build_primary_lists launch");
 }
 
 /* One render launch of a tile set, shared by every entry point up to where its sums go (dst): argument checks, the
@@ -981,7 +1035,18 @@ void render_launch(hrt_scene* s, const hrt_camera* cam, const hrt_render_params*
   }
   size_t tiles_bytes = n_tiles * sizeof(G::TileDev);
   const size_t partial_bytes = n_chunks > 1 || raw ? (size_t)n_chunks * outp * sizeof(float4) : 0;
+  const Plan pl = plan(s, cam, p->flags);
+  const uint32_t list_cap = primary_list_cap(s, pl);
+  const uint32_t n_cells = plist::cells_x(p->width) * plist::cells_y(p->height);
+  const size_t lists_bytes = list_cap ? (size_t)n_cells * sizeof(plist::Record) : 0;
   auto grow = [&](hrt_scene::Slot& g, bool partial) {
+    if (lists_bytes > g.lists_cap) { /* sized at the slot's first use, with its tile table: no timed step allocates */
+      if (g.d_lists) hip_check(hipFree(g.d_lists), "hipFree(lists)");
+      g.d_lists = nullptr;
+      g.lists_cap = 0;
+      hip_check(hipMalloc(&g.d_lists, lists_bytes), "hipMalloc(lists)");
+      g.lists_cap = lists_bytes;
+    }
     if (tiles_bytes > g.tiles_cap) {
       if (g.d_mem) hip_check(hipFree(g.d_mem), "hipFree(slot)");
       if (g.h_tiles) hip_check(hipHostFree(g.h_tiles), "hipHostFree(slot)");
@@ -1005,7 +1070,7 @@ void render_launch(hrt_scene* s, const hrt_camera* cam, const hrt_render_params*
    * partial-sum buffers (a pixel's chunk sums: 1 GB for C2's 32 chunks) only when this call is
    * asynchronous (no stats): a synchronous caller (hrt_render, a progressive batch with stats) never
    * has a second launch in flight, and would otherwise hold N_SLOTS such buffers. */
-  const bool first_growth = tiles_bytes > sl.tiles_cap || partial_bytes > sl.partial_cap;
+  const bool first_growth = tiles_bytes > sl.tiles_cap || partial_bytes > sl.partial_cap || lists_bytes > sl.lists_cap;
   grow(sl, true);
   if (first_growth)
     for (auto& other : s->slots)
@@ -1015,8 +1080,12 @@ void render_launch(hrt_scene* s, const hrt_camera* cam, const hrt_render_params*
   hip_check(hipMemsetAsync(scratch, 0, SLOT_HDR, stream), "hipMemsetAsync");
   hip_check(hipMemcpyAsync((uint8_t*)scratch + SLOT_HDR, (uint8_t*)sl.h_tiles + SLOT_HDR, tiles_bytes, hipMemcpyHostToDevice,
                            stream), "hipMemcpyAsync(tiles)");
-  const Plan pl = plan(s, cam, p->flags);
   KParams kp = scene_params(s, cam, p, pl);
+  kp.cells_x = plist::cells_x(p->width);
+  if (list_cap) {
+    launch_primary_lists(s, kp, list_cap, n_cells, sl.d_lists, stream);
+    kp.prim_lists = (const uint4*)sl.d_lists;
+  }
   kp.tiles = (const G::TileDev*)((uint8_t*)scratch + SLOT_HDR);
   kp.n_tiles = n_tiles;
   kp.total_work = (uint32_t)(pad * n_chunks);

@@ -5,6 +5,7 @@
  * DESIGN.md section 6.1.  Built on its own translation unit (see kernel_common.h).
  */
 #include "kernel_common.h"
+#include "primary_list.h"
 
 using namespace hrt;
 using namespace hrt::lane;
@@ -51,6 +52,9 @@ void render_basic_kernel(KParams P) {
   constexpr bool WS = CULL == G::CULL_EXACT;
   constexpr bool SPEC = WS && HRT_SPEC;
   constexpr int WMEM = HYB ? WM_HYB : (LDS ? WM_LDS : WM_BUF);
+  /* the camera segment's leaf lists (primary_list.h): this instantiation alone, and only when the launch built
+   * them (render.hip render_launch; a null pointer otherwise) */
+  constexpr bool LISTS = WS && LDS && !HYB && !HEAVY && !SPLIT && !C16 && !PACKET;
   constexpr uint32_t STRIDE = LDS ? (uint32_t)sizeof(G::Node) : 1u;
   const uint32_t lds_base = (uint32_t)(size_t)(__attribute__((address_space(3))) float4*)lds_scene;
   const uint32_t root = WS || !LDS ? 0u : lds_base;
@@ -97,6 +101,7 @@ void render_basic_kernel(KParams P) {
   bool has_item = false, exhausted = false;
   bool walking = false; /* a segment is in flight (walk running, or finished and waiting to shade) */
   bool setup = false;   /* the lane's next segment needs its ray set up (a new sample, or a scattered ray) */
+  bool short_prev = false; /* LISTS: the last pass was a short one (wave-uniform) */
   Item it{0u, 0u, 0u, 0u};
   WaveBlock wb{0u, 0u};
 #if HRT_CLAIM_BLOCKS
@@ -141,7 +146,17 @@ void render_basic_kernel(KParams P) {
 #endif
     if (has_item && !had_item) *slot_lds = it.slot;
     if (!__any(has_item || !exhausted)) break;
+    /* LISTS: a lane that starts a sample reads its cell's leaf list (one 16-B load, issued ahead of the sample's
+     * seeding) and consumes it below, once its ray is set up */
+    [[maybe_unused]] uint4 rec = make_uint4(~0u, ~0u, ~0u, ~0u);
+    [[maybe_unused]] bool fresh = false;
     if (has_item && !walking) {
+      if constexpr (LISTS) {
+        if (P.prim_lists) {
+          rec = P.prim_lists[(it.pxy >> 19) * P.cells_x + ((it.pxy & 0xFFFFu) >> 3)];
+          fresh = true;
+        }
+      }
       start_sample(P, ps, it.pxy & 0xFFFFu, it.pxy >> 16, it.sample);
       walking = true;
       setup = true;
@@ -162,6 +177,39 @@ void render_basic_kernel(KParams P) {
 #if HRT_RAY_REDERIVE_SPHERE
     set_dir(r, r.o, r.d); /* every lane: dead across shading (kernel_common.h) */
 #endif
+    /* The camera segment by its cell's leaf list: the lanes with a usable record (a
+     * sample just started, depth left, no overflow, the ray not in NaN mode) take one ordinary node step on each
+     * listed leaf, in leaf order, and the leaf's test where the step passes -- the steps and tests their walk
+     * would make at its leaves, without the inner nodes.  They then hold a finished walk (node = end, nothing
+     * pending).  The entry index is a constant in each round.
+     * A pass whose lists finished some segments is a SHORT pass: it skips the walk loop and shades those lanes at
+     * once, so their scattered rays are set up with the next pass and walk with the wave, instead of waiting out a
+     * walk loop they have no part in (which cost more than the lists saved: DESIGN.md section 10).  A short pass is
+     * never followed by another, so the lanes in the middle of a walk step at least every other pass; lanes listed in
+     * the pass after a short one wait for that pass's shading as every finished lane does. */
+    bool short_pass = false;
+    if constexpr (LISTS) {
+      const bool listed = fresh && ps.depth_left != 0 && (rec.x & 0xFFFFu) != plist::PL_OVERFLOW && !nan_mode(r);
+      if (__ballot(listed)) {
+        const uint32_t ew[4] = {rec.x, rec.y, rec.z, rec.w};
+#pragma unroll
+        for (int j = 0; j < (int)plist::PL_CAP; j++) {
+          const uint32_t e = (ew[j >> 1] >> (16 * (j & 1))) & 0xFFFFu;
+          const bool act = listed && e != plist::PL_UNUSED;
+          if (!__ballot(act)) break;
+          bool pass = false;
+          uint32_t leaf = 0u;
+          if (act) {
+            if constexpr (COUNT) cn.steps++;
+            pass = list_step<COUNT, WMEM>(ws, e << 4, r, tmin_c, closest, cn, leaf);
+          }
+          if (pass) walk_leaf_test<COUNT, WMEM>(P, ws, leaf, r, closest, winner, cn);
+        }
+        if (listed) node = end;
+        short_pass = !short_prev;
+      }
+    }
+    short_prev = short_pass;
     /* step the walks until enough lanes have finished (lanes not walking hold node >= end).  A lane
      * whose leaf box passed holds WALK_PEND in `node` and waits; the wave runs the sphere block
      * once `batch` lanes wait (or no lane can step), instead of for every lane that needs it. */
@@ -170,6 +218,7 @@ void render_basic_kernel(KParams P) {
     const unsigned long long walkers = __ballot(walking);
     uint32_t iters = 0;
     bool stuck = false;
+    if (!short_pass) {
     if constexpr (PACKET) {
       /* the packet walk (render_general.hip PACKET): the wave at ONE position u, the lanes whose own position is u
        * active; a leaf's test runs at once for the lanes that pass its box, so each lane tests exactly its own
@@ -259,6 +308,7 @@ void render_basic_kernel(KParams P) {
       const unsigned long long live = __ballot(node < end || walk_pend<C16>(node) || (SPEC && pend != G::NONE));
       if (!live || (uint32_t)__popcll(walkers & ~live) >= need) break;
       if (++iters > cap) { stuck = true; break; }
+    }
     }
     }
     if (stuck) { /* a walk that cannot end (corrupt scene data): report it, retire the wave */

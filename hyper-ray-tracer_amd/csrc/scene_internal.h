@@ -166,6 +166,8 @@ struct hrt_scene {
     void* event = nullptr; /* hipEvent_t */
     void* d_partial = nullptr; /* sample-chunk sums [pixels][n_chunks] */
     size_t partial_cap = 0;
+    void* d_lists = nullptr; /* the camera segment's per-cell leaf lists (primary_list.h), 16 B per 8x8 pixel cell */
+    size_t lists_cap = 0;
     bool used = false;
   };
   static constexpr int N_SLOTS = 4;
