@@ -1253,18 +1253,23 @@ int oracle_scene_bbox(void* s, float* out6) {
   return 1;
 }
 
-/* counters[0..C_COUNT): segments aabb sphere moving rect medium tex_solid tex_checker tex_noise
- * tex_image samples pixels */
-int oracle_render(void* scene, uint32_t W, uint32_t H, uint32_t spp, uint32_t depth,
-                  uint32_t sample_offset, uint64_t seed, float t_min, uint32_t x0, uint32_t y0,
-                  uint32_t w, uint32_t h, float* out, int nthreads, uint64_t* counters) {
+/* The camera of a render: the preset's own (c == nullptr), or look_from(3) look_at(3) fov aperture
+ * focus_dist time0 time1 (oracle_render_cam / oracle_render_rows_cam) through the same constructor. */
+static Camera make_camera(const Scene& s, const float* c, uint32_t W, uint32_t H) {
+  const PresetInfo& I = s.info;
+  if (!c)
+    return Camera(I.look_from, I.look_at, I.fov, I.aperture, I.focus_dist, I.time0, I.time1, (int)W, (int)H);
+  return Camera(v3(c[0], c[1], c[2]), v3(c[3], c[4], c[5]), c[6], c[7], c[8], c[9], c[10], (int)W, (int)H);
+}
+
+static int render_with(void* scene, const float* cam11, uint32_t W, uint32_t H, uint32_t spp, uint32_t depth,
+                       uint32_t sample_offset, uint64_t seed, float t_min, uint32_t x0, uint32_t y0,
+                       uint32_t w, uint32_t h, float* out, int nthreads, uint64_t* counters) {
   try {
     Scene* s = static_cast<Scene*>(scene);
     if (!s || !out || W < 2 || H < 2 || spp == 0 || x0 + w > W || y0 + h > H)
       throw std::runtime_error("bad render arguments");
-    const PresetInfo& I = s->info;
-    Camera cam(I.look_from, I.look_at, I.fov, I.aperture, I.focus_dist, I.time0, I.time1, (int)W,
-               (int)H);
+    Camera cam = make_camera(*s, cam11, W, H);
     RenderArgs A{W, H, spp, depth, sample_offset, seed, t_min, x0, y0, w, h, out};
     Counters total;
     render(*s, cam, A, nthreads, total);
@@ -1276,22 +1281,43 @@ int oracle_render(void* scene, uint32_t W, uint32_t H, uint32_t spp, uint32_t de
   }
 }
 
+/* counters[0..C_COUNT): segments aabb sphere moving rect medium tex_solid tex_checker tex_noise
+ * tex_image samples pixels */
+int oracle_render(void* scene, uint32_t W, uint32_t H, uint32_t spp, uint32_t depth,
+                  uint32_t sample_offset, uint64_t seed, float t_min, uint32_t x0, uint32_t y0,
+                  uint32_t w, uint32_t h, float* out, int nthreads, uint64_t* counters) {
+  return render_with(scene, nullptr, W, H, spp, depth, sample_offset, seed, t_min, x0, y0, w, h, out, nthreads,
+                     counters);
+}
+
+/* oracle_render from a camera other than the preset's: cam11 = look_from(3) look_at(3) fov aperture
+ * focus_dist time0 time1 (tests/cameras.py) */
+int oracle_render_cam(void* scene, const float* cam11, uint32_t W, uint32_t H, uint32_t spp, uint32_t depth,
+                      uint32_t sample_offset, uint64_t seed, float t_min, uint32_t x0, uint32_t y0,
+                      uint32_t w, uint32_t h, float* out, int nthreads, uint64_t* counters) {
+  if (!cam11) {
+    g_err = "no camera";
+    return 1;
+  }
+  return render_with(scene, cam11, W, H, spp, depth, sample_offset, seed, t_min, x0, y0, w, h, out, nthreads,
+                     counters);
+}
+
 /* Columns [x0, x0 + w) of a set of rows of the W x H frame (bench.py's CPU baseline and parity band:
  * full-width rows spread over the image, so the sample's rays per sample match the frame's; the GPU
  * config tests: short windows of a row).  Same per-pixel computation as render(); the tasks are
  * task_w-pixel row segments (80 = the reference's tile width) on the pool.  out: [n_rows][w][4]. */
-int oracle_render_rows(void* scene, uint32_t W, uint32_t H, uint32_t spp, uint32_t depth,
-                       uint32_t sample_offset, uint64_t seed, float t_min, const uint32_t* rows,
-                       uint32_t n_rows, uint32_t x0, uint32_t w, uint32_t task_w, float* out, int nthreads,
-                       uint64_t* counters) {
+static int render_rows_with(void* scene, const float* cam11, uint32_t W, uint32_t H, uint32_t spp, uint32_t depth,
+                            uint32_t sample_offset, uint64_t seed, float t_min, const uint32_t* rows,
+                            uint32_t n_rows, uint32_t x0, uint32_t w, uint32_t task_w, float* out, int nthreads,
+                            uint64_t* counters) {
   try {
     Scene* s = static_cast<Scene*>(scene);
     if (!s || !out || !rows || W < 2 || H < 2 || spp == 0 || w == 0 || task_w == 0 || x0 + w > W)
       throw std::runtime_error("bad render arguments");
     for (uint32_t r = 0; r < n_rows; r++)
       if (rows[r] >= H) throw std::runtime_error("row outside the image");
-    const PresetInfo& I = s->info;
-    Camera cam(I.look_from, I.look_at, I.fov, I.aperture, I.focus_dist, I.time0, I.time1, (int)W, (int)H);
+    Camera cam = make_camera(*s, cam11, W, H);
     const uint32_t seg = task_w, per_row = (w + seg - 1) / seg, ntasks = per_row * n_rows;
     std::atomic<uint32_t> next(0);
     const int nt = nthreads > 0 ? nthreads : 1;
@@ -1326,6 +1352,26 @@ int oracle_render_rows(void* scene, uint32_t W, uint32_t H, uint32_t spp, uint32
     g_err = e.what();
     return 1;
   }
+}
+
+int oracle_render_rows(void* scene, uint32_t W, uint32_t H, uint32_t spp, uint32_t depth,
+                       uint32_t sample_offset, uint64_t seed, float t_min, const uint32_t* rows,
+                       uint32_t n_rows, uint32_t x0, uint32_t w, uint32_t task_w, float* out, int nthreads,
+                       uint64_t* counters) {
+  return render_rows_with(scene, nullptr, W, H, spp, depth, sample_offset, seed, t_min, rows, n_rows, x0, w, task_w,
+                          out, nthreads, counters);
+}
+
+int oracle_render_rows_cam(void* scene, const float* cam11, uint32_t W, uint32_t H, uint32_t spp, uint32_t depth,
+                           uint32_t sample_offset, uint64_t seed, float t_min, const uint32_t* rows,
+                           uint32_t n_rows, uint32_t x0, uint32_t w, uint32_t task_w, float* out, int nthreads,
+                           uint64_t* counters) {
+  if (!cam11) {
+    g_err = "no camera";
+    return 1;
+  }
+  return render_rows_with(scene, cam11, W, H, spp, depth, sample_offset, seed, t_min, rows, n_rows, x0, w, task_w,
+                          out, nthreads, counters);
 }
 
 /* ---- unit entry points for the KAT fixtures (tests/golden) ---- */

@@ -44,6 +44,10 @@ def load() -> ctypes.CDLL:
     L.oracle_render.argtypes = [vp, u32, u32, u32, u32, u32, u64, f, u32, u32, u32, u32, vp, i32, vp]
     L.oracle_render_rows.restype = i32
     L.oracle_render_rows.argtypes = [vp, u32, u32, u32, u32, u32, u64, f, vp, u32, u32, u32, u32, vp, i32, vp]
+    L.oracle_render_cam.restype = i32
+    L.oracle_render_cam.argtypes = [vp, vp, u32, u32, u32, u32, u32, u64, f, u32, u32, u32, u32, vp, i32, vp]
+    L.oracle_render_rows_cam.restype = i32
+    L.oracle_render_rows_cam.argtypes = [vp, vp, u32, u32, u32, u32, u32, u64, f, vp, u32, u32, u32, u32, vp, i32, vp]
     L.oracle_camera.argtypes = [vp, vp, f, f, f, f, f, i32, i32, vp]
     L.oracle_camera_ray.argtypes = [vp, vp, f, f, f, i32, i32, f, f, vp, f, vp]
     L.oracle_aabb_hit.restype = i32
@@ -66,6 +70,15 @@ def load() -> ctypes.CDLL:
 
 def _p(a):
     return a.ctypes.data
+
+
+def _cam11(camera) -> np.ndarray:
+    """(look_from, look_at, fov, aperture, focus_dist, time0, time1) as the 11 floats oracle_render_cam takes."""
+    look_from, look_at, fov, aperture, focus_dist, time0, time1 = camera
+    c = np.array([*look_from, *look_at, fov, aperture, focus_dist, time0, time1], np.float32)
+    if c.shape != (11,):
+        raise ValueError("camera: (look_from(3), look_at(3), fov, aperture, focus_dist, time0, time1)")
+    return c
 
 
 class OracleScene:
@@ -97,25 +110,37 @@ class OracleScene:
         b = np.zeros(6, np.float32)
         return b if load().oracle_scene_bbox(self.h, _p(b)) else None
 
-    def render(self, width, height, spp, depth=50, seed=1, region=None, threads=8, sample_offset=0, t_min=0.001):
+    def render(self, width, height, spp, depth=50, seed=1, region=None, threads=8, sample_offset=0, t_min=0.001,
+               camera=None):
+        """camera: (look_from, look_at, fov, aperture, focus_dist, time0, time1) in place of the preset's own."""
         x0, y0, w, h = region if region is not None else (0, 0, width, height)
         out = np.zeros((h, w, 4), np.float32)
         cnt = np.zeros(16, np.uint64)
-        st = load().oracle_render(self.h, width, height, spp, depth, sample_offset, seed, t_min, x0, y0, w, h, _p(out), threads, _p(cnt))
+        if camera is None:
+            st = load().oracle_render(self.h, width, height, spp, depth, sample_offset, seed, t_min, x0, y0, w, h, _p(out), threads, _p(cnt))
+        else:
+            c = _cam11(camera)
+            st = load().oracle_render_cam(self.h, _p(c), width, height, spp, depth, sample_offset, seed, t_min, x0, y0, w, h,
+                                          _p(out), threads, _p(cnt))
         if st != 0:
             raise RuntimeError(load().oracle_last_error().decode())
         return out, dict(zip(COUNTERS, [int(c) for c in cnt[: len(COUNTERS)]]))
 
     def render_rows(self, width, height, spp, rows, depth=50, seed=1, threads=8, sample_offset=0, t_min=0.001,
-                    x0=0, w=None, task_w=80):
+                    x0=0, w=None, task_w=80, camera=None):
         """Columns [x0, x0 + w) (default: all) of rows `rows` of the width x height frame, in tasks of
-        task_w pixels: (len(rows), w, 4) f32 and counters."""
+        task_w pixels: (len(rows), w, 4) f32 and counters.  camera: as in render."""
         r = np.ascontiguousarray(rows, np.uint32)
         w = width - x0 if w is None else w
         out = np.zeros((r.size, w, 4), np.float32)
         cnt = np.zeros(16, np.uint64)
-        st = load().oracle_render_rows(self.h, width, height, spp, depth, sample_offset, seed, t_min, _p(r), r.size,
-                                       x0, w, task_w, _p(out), threads, _p(cnt))
+        if camera is None:
+            st = load().oracle_render_rows(self.h, width, height, spp, depth, sample_offset, seed, t_min, _p(r), r.size,
+                                           x0, w, task_w, _p(out), threads, _p(cnt))
+        else:
+            c = _cam11(camera)
+            st = load().oracle_render_rows_cam(self.h, _p(c), width, height, spp, depth, sample_offset, seed, t_min, _p(r),
+                                               r.size, x0, w, task_w, _p(out), threads, _p(cnt))
         if st != 0:
             raise RuntimeError(load().oracle_last_error().decode())
         return out, dict(zip(COUNTERS, [int(c) for c in cnt[: len(COUNTERS)]]))

@@ -4,6 +4,10 @@ Bar (north star): per-pixel L-infinity <= 1e-3 on RGB.  The two sides share ever
 operation (hd_math.h, -ffp-contract=off), so the paths are identical: the device's segment count
 (world.hit calls) must equal the oracle's exactly, and the only RGB difference left is the order in
 which each path's radiance is accumulated (front-to-back on the GPU, recursive in the reference).
+
+Cameras: every case here renders a preset from that preset's own camera with the shutter [0, 1] and t_min 0.001.
+Other viewpoints, lenses, shutters (inside [0, 1] and reaching outside it: plan()'s REFERENCE fallback) and t_min
+values are held to the oracle in tests/test_gpu_cameras.py, from the table of tests/cameras.py.
 """
 import numpy as np
 import pytest

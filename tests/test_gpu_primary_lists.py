@@ -28,11 +28,12 @@ def scenes(earth):
     return get
 
 
-def _render(s, W, H, spp, depth=50, tiles=None, flags=0):
-    """The call's pixels as uint32 (packed tile after tile) and its stats."""
+def _render(s, W, H, spp, depth=50, tiles=None, flags=0, camera=None):
+    """The call's pixels as uint32 (packed tile after tile) and its stats.  camera: a tests/cameras.py spec in place
+    of the preset's own."""
     import torch
 
-    cam = hrt.preset_camera(s.info, W, H)
+    cam = hrt.preset_camera(s.info, W, H) if camera is None else hrt.camera(*camera, W, H)
     p = hrt.params(W, H, spp, depth, SEED, tuple(s.info.background), flags=flags)
     tiles = tiles if tiles is not None else [(0, 0, W, H)]
     n = sum(t[2] * t[3] for t in tiles)

@@ -13,7 +13,8 @@ render_basic_kernel's lane does) and the list walk (list_step per entry, then wa
   ranges, which is what the pads are for.
 
 Presets: random, motion (per-sphere shutters), two_spheres (lens radius 0).  Frames: 1920x1080 on 200 seeded cells,
-all of 40x24 and of 37x23 (not multiples of 8).
+all of 40x24 and of 37x23 (not multiples of 8).  Each from the preset's own camera; tests/test_cameras.py runs the
+same check (_check with camera=) from the cameras of tests/cameras.py.
 
 The overflow cap: no preset may overflow more than 10% of its cells at capacity 8.  It is asserted on the 1920x1080
 frame, the size the lists are made for.  On the two tiny frames a cell's footprint is a fifth of the frame's width
@@ -74,10 +75,11 @@ def _cells(W, H, n=None, seed=7):
     return [(int(i) % cx, int(i) // cx) for i in sorted(pick)]
 
 
-def _check(L, earth, name, W, H, cells, cap=CAP):
-    """Totals of pl_check_cell over the cells, and each cell's leaf count."""
+def _check(L, earth, name, W, H, cells, cap=CAP, camera=None):
+    """Totals of pl_check_cell over the cells, and each cell's leaf count.  camera: a tests/cameras.py spec
+    (look_from, look_at, fov, aperture, focus_dist, time0, time1) in place of the preset's own."""
     s = hrt.preset(name, 1, earth)
-    cam = hrt.preset_camera(s.info, W, H)
+    cam = hrt.preset_camera(s.info, W, H) if camera is None else hrt.camera(*camera, W, H)
     blob, info = hrt.scene_blob(s)
     assert L.pl_listable(ctypes.byref(info)) == 1, name
     p = hrt.params(W, H, SPP, 50, 3, tuple(s.info.background))
