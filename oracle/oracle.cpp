@@ -1133,6 +1133,156 @@ static Scene* build_preset(int preset, uint64_t seed, const uint8_t* img, uint32
   return sc.release();
 }
 
+/* ---------------------------------------------------------------- a scene from a description
+ * The C ABI's constructors (include/hrt/hrt.h hrt_tex_* / hrt_mat_* / hrt_node_*) one to one, in creation order,
+ * assembled from the types above: the only new code is the graph assembly.  The description is an array of u32
+ * words (floats as their IEEE bits) and a byte blob that holds the image textures' pixels.
+ *   header, DESC_HEADER words: DESC_MAGIC, root node id, background(3), then the default camera's 11 floats
+ *                              look_from(3) look_at(3) fov aperture focus_dist time0 time1
+ *   records, until the end of the words: an opcode and its arguments
+ *     D_TEX_SOLID r g b                 D_TEX_CHECKER odd even
+ *     D_TEX_NOISE scale ranvec[768] perm[768]       (the tables oracle_perlin takes: 256 x 3, 3 x 256)
+ *     D_TEX_IMAGE width height components offset    (width * height * components bytes of the blob at
+ *                                                    offset; a product of 0 is the empty image: magenta)
+ *     D_MAT_LAMBERTIAN tex   D_MAT_METAL r g b fuzz   D_MAT_DIELECTRIC ior   D_MAT_DIFFUSE_LIGHT tex
+ *     D_MAT_ISOTROPIC tex
+ *     D_SPHERE c(3) r mat               D_MOVING c0(3) c1(3) t0 t1 r mat
+ *     D_RECT plane a0 a1 b0 b1 k mat    D_CUBOID p0(3) p1(3) mat
+ *     D_TRANSLATE child d(3)            D_ROTATE axis child angle
+ *     D_MEDIUM boundary density tex     D_LIST n child[n]        D_BVH t0 t1 n child[n]
+ * Ids are creation indices per class (textures, materials, nodes), counted from 0 over the records of that
+ * class: one id per node record, a Cuboid's sides and a BvhNode's inner nodes have none.  A node belongs to one
+ * parent (Box<dyn Hittable>): naming it twice, or naming a consumed node as the root, is an error, as are an
+ * id that does not exist yet and a truncated record.  A D_BVH is built where it stands by BvhNode's
+ * constructor with its own (t0, t1), which throws where bvh_node.rs panics (no elements, no bounding box).
+ * A ConstantMedium's medium_id is the number of media created before it, as hrt_node_constant_medium and
+ * Builder::medium count. */
+enum : uint32_t {
+  DESC_MAGIC = 0x3144534Fu, DESC_HEADER = 16,
+  D_TEX_SOLID = 1, D_TEX_CHECKER = 2, D_TEX_NOISE = 3, D_TEX_IMAGE = 4,
+  D_MAT_LAMBERTIAN = 10, D_MAT_METAL = 11, D_MAT_DIELECTRIC = 12, D_MAT_DIFFUSE_LIGHT = 13, D_MAT_ISOTROPIC = 14,
+  D_SPHERE = 20, D_MOVING = 21, D_RECT = 22, D_CUBOID = 23, D_TRANSLATE = 24, D_ROTATE = 25, D_MEDIUM = 26,
+  D_LIST = 27, D_BVH = 28
+};
+
+static Scene* build_desc(const uint32_t* words, uint64_t n_words, const uint8_t* blob, uint64_t n_blob) {
+  if (!words || n_words < DESC_HEADER || words[0] != DESC_MAGIC) throw std::runtime_error("bad scene description header");
+  std::unique_ptr<Scene> sc(new Scene());
+  std::vector<TexP> texs;
+  std::vector<MatP> mats;
+  std::vector<HitP> nodes; /* a consumed node is null */
+  uint64_t at = DESC_HEADER;
+  auto u = [&]() -> uint32_t {
+    if (at >= n_words) throw std::runtime_error("truncated scene description");
+    return words[at++];
+  };
+  auto f = [&]() { return u2f(u()); };
+  auto vec = [&]() { float x = f(), y = f(), z = f(); return v3(x, y, z); };
+  auto tex = [&]() -> TexP {
+    const uint32_t id = u();
+    if (id >= texs.size()) throw std::runtime_error("bad texture id");
+    return texs[id];
+  };
+  auto mat = [&]() -> MatP {
+    const uint32_t id = u();
+    if (id >= mats.size()) throw std::runtime_error("bad material id");
+    return mats[id];
+  };
+  auto take = [&](uint32_t id) -> HitP {
+    if (id >= nodes.size()) throw std::runtime_error("bad node id");
+    if (!nodes[id]) throw std::runtime_error("node already owned by another node");
+    return std::move(nodes[id]);
+  };
+  auto children = [&]() {
+    const uint32_t n = u();
+    std::vector<HitP> c;
+    for (uint32_t i = 0; i < n; i++) c.push_back(take(u()));
+    return c;
+  };
+  while (at < n_words) {
+    const uint32_t op = u();
+    switch (op) {
+      case D_TEX_SOLID: { Vec3 c = vec(); texs.push_back(std::make_shared<SolidColor>(c)); break; }
+      case D_TEX_CHECKER: { TexP o = tex(), e = tex(); texs.push_back(std::make_shared<CheckerTexture>(o, e)); break; }
+      case D_TEX_NOISE: {
+        const float scale = f();
+        if (n_words - at < 1536) throw std::runtime_error("truncated scene description");
+        std::vector<float> rv(768);
+        for (int i = 0; i < 768; i++) rv[i] = u2f(words[at + i]);
+        for (int i = 0; i < 768; i++)
+          if (words[at + 768 + i] >= 256) throw std::runtime_error("permutation entry >= 256");
+        texs.push_back(std::make_shared<NoiseTexture>(std::make_shared<PerlinNoise>(rv.data(), words + at + 768), scale));
+        at += 1536;
+        break;
+      }
+      case D_TEX_IMAGE: {
+        const uint32_t w = u(), h = u(), c = u(), off = u();
+        const uint64_t bytes = (uint64_t)w * h * c;
+        if (bytes && (!blob || off > n_blob || bytes > n_blob - off)) throw std::runtime_error("image outside the blob");
+        if (bytes && c < 3) throw std::runtime_error("image needs >= 3 components");
+        /* image_texture.rs:19-33: the texture owns its pixels (ImageTexture copies them) */
+        texs.push_back(std::make_shared<ImageTexture>(bytes ? blob + off : nullptr, w, h, c));
+        break;
+      }
+      case D_MAT_LAMBERTIAN: mats.push_back(lambert(tex())); break;
+      case D_MAT_METAL: { Vec3 a = vec(); float fz = f(); mats.push_back(std::make_shared<Metal>(a, fz)); break; }
+      case D_MAT_DIELECTRIC: mats.push_back(std::make_shared<Dielectric>(f())); break;
+      case D_MAT_DIFFUSE_LIGHT: mats.push_back(std::make_shared<DiffuseLight>(tex())); break;
+      case D_MAT_ISOTROPIC: mats.push_back(std::make_shared<Isotropic>(tex())); break;
+      case D_SPHERE: { Vec3 c = vec(); float r = f(); nodes.emplace_back(new Sphere(c, r, mat())); break; }
+      case D_MOVING: {
+        Vec3 c0 = vec(), c1 = vec();
+        float t0 = f(), t1 = f(), r = f();
+        nodes.emplace_back(new MovingSphere(c0, c1, t0, t1, r, mat()));
+        break;
+      }
+      case D_RECT: {
+        const uint32_t plane = u();
+        if (plane > 2) throw std::runtime_error("bad plane");
+        float a0 = f(), a1 = f(), b0 = f(), b1 = f(), k = f();
+        nodes.emplace_back(new Rect((int)plane, a0, a1, b0, b1, k, mat()));
+        break;
+      }
+      case D_CUBOID: { Vec3 p0 = vec(), p1 = vec(); nodes.emplace_back(new Cuboid(p0, p1, mat())); break; }
+      case D_TRANSLATE: { HitP c = take(u()); Vec3 d = vec(); nodes.emplace_back(new Translation(std::move(c), d)); break; }
+      case D_ROTATE: {
+        const uint32_t axis = u();
+        if (axis > 2) throw std::runtime_error("bad axis");
+        HitP c = take(u());
+        const float angle = f();
+        nodes.emplace_back(new Rotation((int)axis, std::move(c), angle));
+        break;
+      }
+      case D_MEDIUM: {
+        HitP b = take(u());
+        const float density = f();
+        TexP t = tex();
+        nodes.emplace_back(new ConstantMedium(std::move(b), density, std::move(t), sc->n_media++));
+        break;
+      }
+      case D_LIST: nodes.emplace_back(new List(children())); break;
+      case D_BVH: {
+        const float t0 = f(), t1 = f();
+        nodes.emplace_back(new BvhNode(children(), t0, t1));
+        break;
+      }
+      default: throw std::runtime_error("unknown record in scene description");
+    }
+  }
+  sc->world = take(words[1]);
+  PresetInfo& I = sc->info;
+  const uint32_t* h = words + 2;
+  I.background = v3(u2f(h[0]), u2f(h[1]), u2f(h[2]));
+  I.look_from = v3(u2f(h[3]), u2f(h[4]), u2f(h[5]));
+  I.look_at = v3(u2f(h[6]), u2f(h[7]), u2f(h[8]));
+  I.fov = u2f(h[9]);
+  I.aperture = u2f(h[10]);
+  I.focus_dist = u2f(h[11]);
+  I.time0 = u2f(h[12]);
+  I.time1 = u2f(h[13]);
+  return sc.release();
+}
+
 /* ---------------------------------------------------------------- application.rs:477-495 */
 static Vec3 ray_color(const Ray& ray, Vec3 background, const Hittable& world, uint32_t depth,
                       float t_min, Ctx& ctx) {
@@ -1223,17 +1373,32 @@ extern "C" {
 const char* oracle_last_error(void) { return g_err.c_str(); }
 
 /* info[0..15]: look_from(3) look_at(3) fov aperture focus_dist time0 time1 background(3) n_media */
+static void info_out(const Scene* s, float* info) {
+  if (!info) return;
+  const PresetInfo& I = s->info;
+  float v[16] = {I.look_from.x, I.look_from.y, I.look_from.z, I.look_at.x, I.look_at.y,
+                 I.look_at.z, I.fov, I.aperture, I.focus_dist, I.time0, I.time1,
+                 I.background.x, I.background.y, I.background.z, (float)s->n_media, 0.0f};
+  memcpy(info, v, sizeof(v));
+}
+
 void* oracle_preset_build(int preset, uint64_t seed, const uint8_t* img, uint32_t iw, uint32_t ih,
                           uint32_t ic, float* info) {
   try {
     Scene* s = build_preset(preset, seed, img, iw, ih, ic);
-    if (info) {
-      const PresetInfo& I = s->info;
-      float v[16] = {I.look_from.x, I.look_from.y, I.look_from.z, I.look_at.x, I.look_at.y,
-                     I.look_at.z, I.fov, I.aperture, I.focus_dist, I.time0, I.time1,
-                     I.background.x, I.background.y, I.background.z, (float)s->n_media, 0.0f};
-      memcpy(info, v, sizeof(v));
-    }
+    info_out(s, info);
+    return s;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return nullptr;
+  }
+}
+
+/* A scene from a description (build_desc above documents the words and the blob); info as oracle_preset_build. */
+void* oracle_scene_build(const uint32_t* words, uint64_t n_words, const uint8_t* blob, uint64_t n_blob, float* info) {
+  try {
+    Scene* s = build_desc(words, n_words, blob, n_blob);
+    info_out(s, info);
     return s;
   } catch (const std::exception& e) {
     g_err = e.what();

@@ -35,6 +35,8 @@ def load() -> ctypes.CDLL:
     L.oracle_last_error.restype = ctypes.c_char_p
     L.oracle_preset_build.restype = vp
     L.oracle_preset_build.argtypes = [i32, u64, vp, u32, u32, u32, vp]
+    L.oracle_scene_build.restype = vp
+    L.oracle_scene_build.argtypes = [vp, u64, vp, u64, vp]
     L.oracle_scene_destroy.argtypes = [vp]
     L.oracle_scene_count.restype = u32
     L.oracle_scene_count.argtypes = [vp]
@@ -91,6 +93,25 @@ class OracleScene:
         self.h = L.oracle_preset_build(preset, scene_seed, _p(img), w, h, c, _p(info))
         if not self.h:
             raise RuntimeError(L.oracle_last_error().decode())
+        self._set_info(info)
+
+    @classmethod
+    def from_description(cls, words: np.ndarray, blob: np.ndarray | None = None) -> "OracleScene":
+        """A scene from a description instead of a preset number: the u32 words and the image byte blob of
+        oracle.cpp build_desc (tests/scene_desc.py Desc.to_oracle encodes them)."""
+        L = load()
+        self = cls.__new__(cls)
+        w = np.ascontiguousarray(words, np.uint32).reshape(-1)
+        b = np.zeros(1, np.uint8) if blob is None or len(blob) == 0 else np.ascontiguousarray(blob, np.uint8).reshape(-1)
+        n_blob = 0 if blob is None else len(blob)
+        info = np.zeros(16, np.float32)
+        self.h = L.oracle_scene_build(_p(w), w.size, _p(b), n_blob, _p(info))
+        if not self.h:
+            raise RuntimeError(L.oracle_last_error().decode())
+        self._set_info(info)
+        return self
+
+    def _set_info(self, info):
         self.look_from, self.look_at = info[0:3].copy(), info[3:6].copy()
         self.fov, self.aperture, self.focus_dist, self.time0, self.time1 = [float(x) for x in info[6:11]]
         self.background = info[11:14].copy()

@@ -63,6 +63,7 @@ struct WideStats {
 WideTree* g_wide = nullptr;
 /* segment recorder (scripts/price_hierarchy.py): origin, direction, final closest of every sphere-lane segment */
 std::vector<float>* g_segs = nullptr;
+bool g_heavy = true; /* the sphere lane's shade_walk instantiation (lane_sim_render sets it per scene) */
 int g_wide_arity = 4; /* 2: a record holds its node's two child boxes (no collapse) */
 WideStats g_ws;
 struct LockKey {
@@ -289,7 +290,10 @@ void render_pixel(const KParams& P, uint32_t px, uint32_t py, float* rgba, uint6
             WalkSrc src;
             src.base = P.walk;
           src.half = P.walk_half;
-            done = !traced || shade_walk<true, WM_HOST, true>(P, src, ps, winner, closest, r.o, r.d, r.time, r.tau, sum, cn) ||
+            /* HEAVY as render.hip plan() instantiates the sphere kernel: only for a scene with noise / image textures */
+            done = !traced ||
+                   (g_heavy ? shade_walk<true, WM_HOST, true>(P, src, ps, winner, closest, r.o, r.d, r.time, r.tau, sum, cn)
+                            : shade_walk<true, WM_HOST, false>(P, src, ps, winner, closest, r.o, r.d, r.time, r.tau, sum, cn)) ||
                    ps.depth_left == 0;
           } else {
             done = !traced ||
@@ -393,6 +397,7 @@ int lane_sim_render(const void* blob, const hrt_blob_info* bi, const hrt_camera*
   P.background = v3(p->background[0], p->background[1], p->background[2]);
   P.seed = p->seed;
   if (kernel == 0 && (bi->feature_mask & ~(G::F_BASIC | G::F_HEAVY_TEX)) != 0) return 1; /* not a sphere scene */
+  g_heavy = (bi->feature_mask & ~G::F_BASIC) != 0; /* render.hip plan(): pl.heavy */
   if (kernel == 3 && (bi->walk_bytes == 0 || !bi->walk_general)) return 1; /* no general stream */
   if (kernel == 0 && bi->walk_general && cull == G::CULL_EXACT) return 1;      /* no sphere stream */
   for (uint32_t y = 0; y < h; y++)

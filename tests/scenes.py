@@ -1,7 +1,9 @@
 """Test scenes built through the C ABI's constructors (hrt_tex_* / hrt_mat_* / hrt_node_*), for kernel-choice
 and stream-layout cases the reference presets do not reach.  Test infrastructure: they have no oracle preset,
-so the tests hold the default path to the verbatim reference traversal (HRT_RENDER_REFERENCE_CULL, the
-segment kernel walking the reference node stream, itself held to the oracle on every preset) bit for bit.
+so tests/test_custom_scenes.py holds the default path to the verbatim reference traversal
+(HRT_RENDER_REFERENCE_CULL, the segment kernel walking the reference node stream, itself held to the oracle on
+every preset) bit for bit; recorded on a tests/scene_desc.py Desc (the builders' `s` argument) the same scenes are
+built by the oracle too, and tests/scenes_oracle.py holds them to it.
 
 - sphere_lists: a sphere-only scene whose BvhNodes hold Lists (application.rs never builds one, but
   BvhNode::new takes any Hittable, bvh_node.rs:27-63, and List::hit tests its members with no box of their
@@ -37,10 +39,11 @@ def _mat(s, rng, kind):
     return s.dielectric(1.5)
 
 
-def sphere_lists(seed=5):
-    """Random-scene-like spheres grouped into Lists inside a BvhNode (application.rs:497-565 materials)."""
+def sphere_lists(seed=5, s=None):
+    """Random-scene-like spheres grouped into Lists inside a BvhNode (application.rs:497-565 materials).
+    s: the builder the constructors are called on (a fresh hrt.Scene, or a tests/scene_desc.py Desc)."""
     rng = np.random.default_rng(seed)
-    s = hrt.Scene()
+    s = hrt.Scene() if s is None else s
     checker = s.checker(s.solid(0.2, 0.3, 0.1), s.solid(0.9, 0.9, 0.9))
     objs = [s.sphere((0, -1000, 0), 1000, s.lambertian(checker))]
     cells = [(a, b) for a in range(-6, 6) for b in range(-6, 6)]
@@ -70,11 +73,11 @@ def sphere_lists(seed=5):
     return s
 
 
-def big_textured(seed=7, grid=26):
+def big_textured(seed=7, grid=26, s=None):
     """grid^2 small spheres (over the LDS budget from grid ~ 18) on a Perlin-noise ground, an image-textured
-    earth and a noise-textured sphere among them (application.rs:589-612 textures)."""
+    earth and a noise-textured sphere among them (application.rs:589-612 textures).  s: as in sphere_lists."""
     rng = np.random.default_rng(seed)
-    s = hrt.Scene()
+    s = hrt.Scene() if s is None else s
     rv, perm = perlin_tables(seed)
     noise = s.noise(4.0, rv, perm)
     objs = [s.sphere((0, -1000, 0), 1000, s.lambertian(noise))]
@@ -92,13 +95,14 @@ def big_textured(seed=7, grid=26):
     return s
 
 
-def foggy(seed=3):
+def foggy(seed=3, s=None):
     """Constant media of every shape the general walk stream distinguishes (constant_medium.rs:34-76), among
     spheres, rects and a light: a world-level medium over one sphere and one over a MOVING sphere (flat GL_MED
     programs), a medium that is a box-less List member (its program is the medium node alone), a medium over a
-    Cuboid (two boundary walks) and a fog sphere around the whole scene, as in application.rs:884-895."""
+    Cuboid (two boundary walks) and a fog sphere around the whole scene, as in application.rs:884-895.
+    s: as in sphere_lists."""
     rng = np.random.default_rng(seed)
-    s = hrt.Scene()
+    s = hrt.Scene() if s is None else s
     white = s.solid(0.73, 0.73, 0.73)
     objs = [s.sphere((0, -1000, 0), 1000, s.lambertian(s.checker(s.solid(0.2, 0.3, 0.1), white)))]
     objs.append(s.rect(hrt.PLANE_ZX, -2, 2, -2, 2, 6.0, s.diffuse_light(s.solid(7, 7, 7))))

@@ -8,13 +8,15 @@ ADVICE r03:
   List around a nested BvhNode of its own Lists keeps the outer box whole (scene.cpp gwalk_leaves_grouped);
 - a textured sphere scene whose walk stream exceeds the LDS budget runs the HEAVY walk over the staged
   part plus global memory (render_sphere.hip launch_sphere), not over LDS it does not own.
-CPU tests check the stream; -m gpu tests hold the default path to the verbatim reference traversal bit for bit.
+CPU tests check the stream; -m gpu tests hold the default path to the verbatim reference traversal bit for bit, and
+to the oracle's render of the same scene (recorded on a tests/scene_desc.py Desc, which builds both).
 """
 import numpy as np
 import pytest
 
 import hrt
 import scenes
+from scene_desc import Desc
 
 
 def _groups_contiguous(leaves):
@@ -67,6 +69,22 @@ def test_big_textured_stream_is_beyond_lds():
     assert info.walk_general == 0 and info.walk_hot > 0 and info.walk_bytes > info.walk_hot
 
 
+def _recorded(make):
+    """The scene of builder `make` recorded on a Desc, and the library's scene replayed from the record."""
+    d = Desc()
+    make(s=d)
+    return d, d.to_hrt()
+
+
+def _oracle_equal(d, a, st, w, h, spp):
+    """The frame `a` of _reference_equal against the oracle's render of the same description (the project's bar)."""
+    ref, cnt = d.to_oracle().render(w, h, spp, 50, seed=11)
+    linf = float(np.abs(a - ref).max())
+    print(f"segments {st.segments} (oracle {cnt['segments']}), L-inf {linf:.3g}")
+    assert st.segments == cnt["segments"]
+    assert linf <= 1e-3
+
+
 def _reference_equal(s, w, h, spp, monkeypatch, kernels=("segment",)):
     s.commit()
     cam = scenes.camera(w, h)
@@ -86,15 +104,18 @@ def _reference_equal(s, w, h, spp, monkeypatch, kernels=("segment",)):
 
 @pytest.mark.gpu
 def test_sphere_lists_on_gpu_equal_reference_traversal(monkeypatch):
-    a, st = _reference_equal(scenes.sphere_lists(), 160, 90, 24, monkeypatch, ("segment", "persistent"))
+    d, s = _recorded(scenes.sphere_lists)
+    a, st = _reference_equal(s, 160, 90, 24, monkeypatch, ("segment", "persistent"))
     assert st.prim_slots == 0  # counters off; the default ran the general walk kernel (no sphere payload reads)
+    _oracle_equal(d, a, st, 160, 90, 24)
 
 
 @pytest.mark.gpu
 def test_big_textured_hybrid_heavy_equals_reference_traversal(monkeypatch):
-    s = scenes.big_textured()
-    _reference_equal(s, 160, 90, 16, monkeypatch)
+    d, s = _recorded(scenes.big_textured)
+    a, st = _reference_equal(s, 160, 90, 16, monkeypatch)
     assert s.scene_info().in_lds == 2  # the stream's staged part in LDS, the rest in global memory
+    _oracle_equal(d, a, st, 160, 90, 16)
 
 
 @pytest.mark.gpu
@@ -103,4 +124,6 @@ def test_foggy_media_shapes_equal_reference_traversal(monkeypatch):
     member, a Cuboid boundary, a fog around the scene) on the GPU: the general walk kernel bit for bit equal to
     the verbatim reference traversal and to the segment kernel (tests/test_lane_sim.py runs the same on the
     host lanes)."""
-    _reference_equal(scenes.foggy(), 120, 72, 16, monkeypatch, ("segment",))
+    d, s = _recorded(scenes.foggy)
+    a, st = _reference_equal(s, 120, 72, 16, monkeypatch, ("segment",))
+    _oracle_equal(d, a, st, 120, 72, 16)
