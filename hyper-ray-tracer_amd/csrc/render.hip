@@ -455,9 +455,12 @@ Plan plan(const hrt_scene* s, const hrt_camera* cam, uint32_t flags) {
                     : (s->g_nodes.size() * sizeof(G::Node) + s->g_prims.size() * sizeof(G::Prim));
   /* the sphere kernel under CULL_EXACT stages the walk stream (layout.h) instead: whole, or its top
    * levels (w_hot) when it exceeds the LDS budget */
-  if (!pl.full && !pl.fast && pl.cull == G::CULL_EXACT) pl.smem = s->w_hot ? s->w_hot : s->w_end;
-  pl.lds = (flags & HRT_RENDER_NO_LDS) == 0 && pl.smem <= (pl.fast ? LDS_FAST_MAX : LDS_SCENE_MAX);
+  /* (not under HRT_KERNEL=general: the segment kernel stages the reference stream, sized above, and a hybrid
+   * stream's w_hot is smaller than that stream) */
   const char* k = knob_env("HRT_KERNEL");
+  if (!pl.full && !pl.fast && pl.cull == G::CULL_EXACT && !(k && strcmp(k, "general") == 0))
+    pl.smem = s->w_hot ? s->w_hot : s->w_end;
+  pl.lds = (flags & HRT_RENDER_NO_LDS) == 0 && pl.smem <= (pl.fast ? LDS_FAST_MAX : LDS_SCENE_MAX);
   /* General scenes run the segment-at-a-time kernel by default; render_full_kernel (persistent walks)
    * is opt-in (HRT_KERNEL=persistent) until it has been measured and validated on the GPU.  Sphere
    * scenes can be sent to the segment kernel for diagnostics (HRT_KERNEL=general). */

@@ -34,7 +34,9 @@ template <bool HEAVY>
 constexpr int sphere_waves() { return HEAVY ? HRT_HEAVY_WAVES : BASIC_WAVES; }
 
 /* HYB (CULL_EXACT with LDS): the walk stream exceeds the LDS budget; its first P.walk_hot bytes (the
- * hierarchy's top levels) are staged, the rest is read through the buffer descriptor (layout.h) */
+ * hierarchy's top levels) are staged, the rest is read through the buffer descriptor (layout.h).  HYB without
+ * LDS (HRT_RENDER_NO_LDS on a hybrid stream with split node parts): the hybrid LAYOUT, nothing staged, every
+ * read through the buffer descriptor */
 /* SPLIT: the stream's node parts are split (layout.h WALK_SPLIT_HALF; hybrid streams: WALK_SPLIT_HALF_HYB) */
 /* C16: 16-B node parts (layout.h WALK_C16; hybrid streams): walk positions are node indices */
 /* PACKET: a tiny stream staged whole in LDS (at most SPHERE_PACKET_NODES node parts: Earth + Perlin, the two-sphere
@@ -51,7 +53,7 @@ void render_basic_kernel(KParams P) {
    * position is the node's LDS byte address, basic_box STRIDE) */
   constexpr bool WS = CULL == G::CULL_EXACT;
   constexpr bool SPEC = WS && HRT_SPEC;
-  constexpr int WMEM = HYB ? WM_HYB : (LDS ? WM_LDS : WM_BUF);
+  constexpr int WMEM = HYB && LDS ? WM_HYB : (LDS ? WM_LDS : WM_BUF);
   /* the camera segment's leaf lists (primary_list.h): this instantiation alone, and only when the launch built
    * them (render.hip render_launch; a null pointer otherwise) */
   constexpr bool LISTS = WS && LDS && !HYB && !HEAVY && !SPLIT && !C16 && !PACKET;
@@ -416,11 +418,16 @@ void launch_sphere(int cull, bool count, bool lds, bool heavy, bool packet, cons
                    : launch_basic<G::CULL_EXACT, false, true, true, false, false, true>(kp, device, stream, smem);
     else count ? launch_basic<G::CULL_EXACT, true, false, false, false, false, true>(kp, device, stream, 0)
                : launch_basic<G::CULL_EXACT, false, false, false, false, false, true>(kp, device, stream, 0);
+  } else if (cull == G::CULL_EXACT && kp.walk_half == G::WALK_SPLIT_HALF_HYB) {
+    /* split node parts of a hybrid stream (layout.h WALK_SPLIT_HALF_HYB, opt-in): the distance to a part's second
+     * half belongs to the stream's layout (kp.walk_half), not to where the stream sits, so a launch that stages
+     * nothing (HRT_RENDER_NO_LDS: walk_hot 0) reads the same layout through the buffer descriptor */
+    if (lds && kp.walk_hot > 0) count ? launch_basic<G::CULL_EXACT, true, true, true, false, true>(kp, device, stream, smem)
+                                      : launch_basic<G::CULL_EXACT, false, true, true, false, true>(kp, device, stream, smem);
+    else count ? launch_basic<G::CULL_EXACT, true, false, true, false, true>(kp, device, stream, 0)
+               : launch_basic<G::CULL_EXACT, false, false, true, false, true>(kp, device, stream, 0);
   } else if (cull == G::CULL_EXACT && lds && kp.walk_hot > 0) { /* top levels in LDS, the rest in global memory */
-    if (kp.walk_half != 16u) { /* split node parts (layout.h WALK_SPLIT_HALF_HYB, opt-in) */
-      if (count) launch_basic<G::CULL_EXACT, true, true, true, false, true>(kp, device, stream, smem);
-      else launch_basic<G::CULL_EXACT, false, true, true, false, true>(kp, device, stream, smem);
-    } else if (count) launch_basic<G::CULL_EXACT, true, true, true>(kp, device, stream, smem);
+    if (count) launch_basic<G::CULL_EXACT, true, true, true>(kp, device, stream, smem);
     else launch_basic<G::CULL_EXACT, false, true, true>(kp, device, stream, smem);
   } else if (cull == G::CULL_EXACT && kp.walk_half != 16u) { /* split node parts (layout.h; F_BASIC scenes) */
     if (count) lds ? launch_basic<G::CULL_EXACT, true, true, false, false, true>(kp, device, stream, smem)

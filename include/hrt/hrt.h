@@ -86,7 +86,9 @@ enum {
   HRT_RENDER_NO_LDS = 2,     /* keep the scene in global memory even when it fits in LDS (A/B) */
   HRT_RENDER_REFERENCE_CULL = 8, /* aabb.rs's per-axis box test alone (the verbatim reference traversal) */
   HRT_RENDER_FAST_CULL = 16,     /* APPROXIMATE: plain slab culling; differs from the reference on ~1e-7 of
-                                    rays (f32 grazing hits the reference accepts outside a box) */
+                                    rays (f32 grazing hits the reference accepts outside a box).  Ignored where a
+                                    bounding box does not hold its geometry (a ZX rect whose two extents differ:
+                                    rect.rs:97-102) and for a shutter outside the boxes' interval */
   HRT_RENDER_SAH = 32            /* APPROXIMATE, with FAST_CULL on sphere-only scenes: SAH octant streams
                                     (traversal order changes which of two near-equal f32 hits wins) */
 };
