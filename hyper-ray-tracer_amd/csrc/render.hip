@@ -1733,6 +1733,39 @@ hrt_status hrt_debug_accumulate(int32_t on_device, const float* partial, uint32_
   });
 }
 
+hrt_status hrt_debug_walk_regroup(int32_t builder, const float* boxes, uint32_t n, uint32_t dp_sub, int32_t* leaf,
+                                  uint32_t* end, uint32_t* depth, float* node_boxes) {
+  return hguard([&] {
+    if (!boxes || !leaf || !end || !depth || !node_boxes || builder < 0 || builder > 4 || n == 0 ||
+        ((builder == 1 || builder == 2) && n > 2048))
+      throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_walk_regroup: bad argument"};
+    std::vector<host::WalkLeaf> leaves(n);
+    for (uint32_t i = 0; i < n; i++) {
+      const float* b = boxes + 6 * (size_t)i;
+      /* the condition under which walk_leaves clears regroup_ok (scene.cpp) */
+      for (int k = 0; k < 3; k++)
+        if (!(b[k] <= b[3 + k]) || !std::isfinite(b[k]) || !std::isfinite(b[3 + k]))
+          throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_walk_regroup: a box is not finite or has min > max"};
+      host::WalkLeaf& L = leaves[i];
+      L.box.mn = v3(b[0], b[1], b[2]);
+      L.box.mx = v3(b[3], b[4], b[5]);
+      L.nobox = false;
+      L.prim = i;
+    }
+    std::vector<host::WNode> T;
+    if (builder == 4) device_walk_regroup(leaves, T, -1); /* the calling thread's current device */
+    else host_walk_regroup(leaves, T, builder, dp_sub);
+    if (T.size() != 2 * (size_t)n - 1) throw HipError{HRT_ERR_STATE, "hrt_debug_walk_regroup: the builder left no full tree"};
+    for (size_t i = 0; i < T.size(); i++) {
+      leaf[i] = T[i].leaf;
+      end[i] = T[i].end;
+      depth[i] = T[i].depth;
+      const float o[6] = {T[i].box.mn.x, T[i].box.mn.y, T[i].box.mn.z, T[i].box.mx.x, T[i].box.mx.y, T[i].box.mx.z};
+      memcpy(node_boxes + 6 * i, o, sizeof(o));
+    }
+  });
+}
+
 hrt_status hrt_debug_sample_chunks(hrt_scene* s, const hrt_render_params* p, uint32_t* out4) {
   return hguard([&] {
     if (!s || !p || !out4) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_sample_chunks: null argument"};

@@ -738,12 +738,12 @@ bool walk_regroup_dp(std::vector<WNode>& T, const std::vector<WalkLeaf>& all, in
 }
 
 /* re-grouped hierarchy over leaves[0, n), iterative, pre-order (a range of n leaves is 2n - 1 nodes) */
-void walk_regroup(std::vector<WNode>& T, const std::vector<WalkLeaf>& leaves, const hrt_camera* view = nullptr) {
-  /* default: the DP (mode 1) for sequences of at most 700 leaves (O(n^3 / 6) work: ~30 ms at Random's 485),
-   * the greedy split above that (and on the device, build_walk.hip).  With a view (hrt_scene_set_view) the
-   * DP's node cost mixes in the view's camera rays (walk_regroup_dp); leaves without a box keep it off. */
-  const char* dp = knob_env("HRT_WALK_DP");
-  const int mode = dp ? dp[0] - '0' : (leaves.size() <= 700 ? 1 : 3);
+/* mode 0: the greedy split; 1 | 2: the DP (walk_regroup_dp; sequences it does not take fall to the greedy split);
+ * 3: the greedy split, and each range of at most dp_sub leaves it reaches re-grouped by the DP (mode 1).  With a
+ * view (hrt_scene_set_view) the DP's node cost mixes in the view's camera rays (walk_regroup_dp); leaves without
+ * a box keep it off. */
+void walk_regroup(std::vector<WNode>& T, const std::vector<WalkLeaf>& leaves, int mode, uint32_t dp_sub,
+                  const hrt_camera* view = nullptr) {
   ViewRays vr;
   double area_root = 0.0;
   bool boxes = !leaves.empty();
@@ -756,10 +756,7 @@ void walk_regroup(std::vector<WNode>& T, const std::vector<WalkLeaf>& leaves, co
   }
   const ViewRays* vp = area_root > 0.0 ? &vr : nullptr;
   if ((mode == 1 || mode == 2) && walk_regroup_dp(T, leaves, mode, 0, 0xFFFFFFFFu, 0, vp, area_root)) return;
-  /* mode 3 (default above 700 leaves): the greedy split below, and each range of at most DP_SUB leaves it
-   * reaches re-grouped by the DP (mode 1) */
-  const char* ds = knob_env("HRT_WALK_DP_SUB");
-  const uint32_t dp_sub = mode == 3 ? (ds ? (uint32_t)atoi(ds) : 256u) : 0u;
+  if (mode != 3) dp_sub = 0u;
   struct Range { uint32_t lo, hi, depth; };
   std::vector<Range> todo{{0u, (uint32_t)leaves.size(), 0u}};
   std::vector<Aabb> pre, suf;
@@ -794,6 +791,16 @@ void walk_regroup(std::vector<WNode>& T, const std::vector<WalkLeaf>& leaves, co
     todo.push_back({r.lo + best + 1, r.hi, r.depth + 1}); /* right after left */
     todo.push_back({r.lo, r.lo + best + 1, r.depth + 1});
   }
+}
+
+/* walk_regroup as commit runs it: HRT_WALK_DP selects the mode (default: the DP, mode 1, for sequences of at most
+ * 700 leaves (O(n^3 / 6) work: ~30 ms at Random's 485), mode 3 above that; the device build, build_walk.hip, makes
+ * mode 0's cuts), HRT_WALK_DP_SUB mode 3's range size (default 256) */
+void walk_regroup_env(std::vector<WNode>& T, const std::vector<WalkLeaf>& leaves, const hrt_camera* view = nullptr) {
+  const char* dp = knob_env("HRT_WALK_DP");
+  const int mode = dp ? dp[0] - '0' : (leaves.size() <= 700 ? 1 : 3);
+  const char* ds = knob_env("HRT_WALK_DP_SUB");
+  walk_regroup(T, leaves, mode, mode == 3 ? (ds ? (uint32_t)atoi(ds) : 256u) : 0u, view);
 }
 
 void put4(std::vector<float>& o, size_t at, float a, float b, float c, float d) {
@@ -1804,7 +1811,7 @@ void build_walk(hrt_scene* s) {
       T.clear();
       /* general streams keep the surface-area DP: with the view's rays Final walks 64.4 -> 65.4 node visits per
        * segment (lane simulator); the view still places their staged part */
-      walk_regroup(T, leaves, nullptr);
+      walk_regroup_env(T, leaves, nullptr);
       s->w_build_us = (uint32_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
       s->w_regrouped = true;
     }
@@ -1824,7 +1831,7 @@ void build_walk(hrt_scene* s) {
       s->w_general = true;
       if (gok && s->opts.walk_tree == 0) {
         TG.clear();
-        walk_regroup(TG, gl, nullptr); /* general stream: the surface-area DP (above) */
+        walk_regroup_env(TG, gl, nullptr); /* general stream: the surface-area DP (above) */
         s->w_regrouped = true;
       }
       walk_place_and_write(s, TG, gl);
@@ -1838,7 +1845,7 @@ void build_walk(hrt_scene* s) {
   else if (regroup) {
     const auto t0 = std::chrono::steady_clock::now();
     T.clear();
-    walk_regroup(T, leaves, s->has_view ? &s->view : nullptr);
+    walk_regroup_env(T, leaves, s->has_view ? &s->view : nullptr);
     s->w_build_us = (uint32_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
     s->w_regrouped = true;
   }
@@ -1847,6 +1854,11 @@ void build_walk(hrt_scene* s) {
 
 }  // namespace hrt
 namespace hrt {
+/* hrt_debug_walk_regroup (render.hip): one host builder on bare leaf boxes, the code build_walk runs */
+void host_walk_regroup(const std::vector<host::WalkLeaf>& leaves, std::vector<host::WNode>& T, int mode, uint32_t dp_sub) {
+  T.clear();
+  walk_regroup(T, leaves, mode, dp_sub, nullptr);
+}
 void flatten_scene(hrt_scene* s) { flatten(s); }
 void flatten_scene_reference(hrt_scene* s) { flatten_reference(s); }
 

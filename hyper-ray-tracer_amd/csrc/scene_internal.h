@@ -198,5 +198,7 @@ std::vector<host::WalkLeaf> gwalk_leaves(const hrt_scene* s, std::vector<host::W
 std::vector<host::WalkLeaf> gwalk_leaves_grouped(const hrt_scene* s, std::vector<host::WNode>* ref_tree, bool* regroup_ok);
 /* build_walk.hip: the re-grouped hierarchy (scene.cpp walk_regroup's splits) built on the device */
 void device_walk_regroup(const std::vector<host::WalkLeaf>& leaves, std::vector<host::WNode>& T, int device);
+/* scene.cpp: walk_regroup (mode and dp_sub as HRT_WALK_DP / HRT_WALK_DP_SUB select them at commit), without a view */
+void host_walk_regroup(const std::vector<host::WalkLeaf>& leaves, std::vector<host::WNode>& T, int mode, uint32_t dp_sub);
 void device_release(hrt_scene* s);
 }  // namespace hrt

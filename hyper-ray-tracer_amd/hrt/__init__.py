@@ -153,7 +153,7 @@ OPTIONAL = {"hrt_abi_version", "hrt_last_launch", "hrt_debug_box_test", "hrt_sce
             "hrt_debug_sample_chunks", "hrt_scene_set_view",
             "hrt_accum_create", "hrt_accum_destroy", "hrt_accum_reset", "hrt_accum_add", "hrt_accum_add_resolve",
             "hrt_accum_samples", "hrt_accum_resolve", "hrt_accum_resolve_host", "hrt_accum_merge", "hrt_accum_download",
-            "hrt_accum_upload", "hrt_debug_accumulate"}
+            "hrt_accum_upload", "hrt_debug_accumulate", "hrt_debug_walk_regroup"}
 HRT_LIB_OVERRIDE = bool(os.environ.get("HRT_LIB"))
 
 # Every entry point of include/hrt/hrt.h (tests/test_abi.py checks the header against this list).
@@ -170,7 +170,7 @@ EXPORTS = [
     "hrt_debug_sample_chunks", "hrt_scene_set_view",
     "hrt_accum_create", "hrt_accum_destroy", "hrt_accum_reset", "hrt_accum_add", "hrt_accum_add_resolve", "hrt_accum_samples",
     "hrt_accum_resolve", "hrt_accum_resolve_host", "hrt_accum_merge", "hrt_accum_download", "hrt_accum_upload",
-    "hrt_debug_accumulate",
+    "hrt_debug_accumulate", "hrt_debug_walk_regroup",
 ]
 
 ABI_VERSION = 6  # include/hrt/hrt.h HRT_ABI_VERSION: the struct layouts below
@@ -262,6 +262,7 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "hrt_accum_download": (S, [vp, vp, vp, u32, _U32P]),
         "hrt_accum_upload": (S, [vp, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams), vp, vp, u32]),
         "hrt_debug_accumulate": (S, [i32, vp, u32, u32, vp, u64, i32, vp]),
+        "hrt_debug_walk_regroup": (S, [i32, vp, u32, u32, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         if name in OPTIONAL and HRT_LIB_OVERRIDE and not hasattr(L, name):
@@ -640,6 +641,22 @@ def debug_accumulate(partial: np.ndarray, acc: np.ndarray, samples: int = 0, fmt
     _check(load().hrt_debug_accumulate(1 if on_device else 0, pa.ctypes.data, n_chunks, n, a.ctypes.data, int(samples),
                                        -1 if fmt is None else _ACCUM_FORMATS[fmt], None if out is None else out.ctypes.data))
     return a, out
+
+
+WALK_GREEDY, WALK_DP_AREA, WALK_DP_LEAVES, WALK_GREEDY_SUB, WALK_DEVICE = range(5)
+
+
+def walk_regroup(boxes: np.ndarray, builder: int, dp_sub: int = 0, out=None):
+    """hrt_debug_walk_regroup: one builder of the walk hierarchy (WALK_*) on (n, 6) float32 leaf boxes (min xyz,
+    max xyz).  Returns the 2n - 1 pre-order nodes as (leaf int32, end uint32, depth uint32, boxes (2n - 1, 6)
+    float32); `out`: such a tuple of arrays to write into."""
+    b = np.ascontiguousarray(boxes, np.float32).reshape(-1, 6)
+    m = max(2 * len(b) - 1, 1)
+    leaf, end, depth, nb = out if out is not None else (np.zeros(m, np.int32), np.zeros(m, np.uint32),
+                                                        np.zeros(m, np.uint32), np.zeros((m, 6), np.float32))
+    _check(load().hrt_debug_walk_regroup(int(builder), b.ctypes.data, len(b), int(dp_sub), leaf.ctypes.data, end.ctypes.data,
+                                         depth.ctypes.data, nb.ctypes.data))
+    return leaf, end, depth, nb
 
 
 def last_launch() -> Optional[dict]:

@@ -471,6 +471,15 @@ hrt_status hrt_debug_box_test(int32_t form, int32_t on_device, const float* boxe
  * that check the arithmetic without a GPU and hold the device to the host bit for bit. */
 hrt_status hrt_debug_accumulate(int32_t on_device, const float* partial, uint32_t n_chunks, uint32_t n, float* acc_inout,
                                 uint64_t samples, int32_t format, void* out);
+/* One builder of the sphere walk stream's hierarchy on n bare leaf boxes (n x 6 floats: min
+ * xyz, max xyz), the code commit runs: builder 0 the host's greedy split, 1 the host's DP over 2 x half area, 2 the
+ * host's DP over half area x leaves, 3 the greedy split with the DP (1) on ranges of at most dp_sub leaves, 4 the
+ * device build on the calling thread's current HIP device.  Writes the 2n - 1 nodes in pre-order: leaf[i] the leaf
+ * index or -1 for an inner node, end[i], depth[i], node_boxes 6 floats per node.  A box that is not finite or has
+ * min > max, n == 0, and n > 2048 for builders 1 and 2 are HRT_ERR_INVALID_ARG, and nothing is written.  Used by
+ * the tests that hold the builders to a restatement of their cut rules and the device build to the host's. */
+hrt_status hrt_debug_walk_regroup(int32_t builder, const float* boxes, uint32_t n, uint32_t dp_sub, int32_t* leaf,
+                                  uint32_t* end, uint32_t* depth, float* node_boxes);
 
 #ifdef __cplusplus
 }
