@@ -133,7 +133,9 @@ struct alignas(16) TileDev {
   uint32_t bw;        /* ceil(w / 8) */
   uint32_t pad_start; /* first padded work index of this tile */
   uint32_t out_off;   /* first output pixel of this tile */
-  uint32_t pad;
+  uint32_t acc_off;   /* first pixel of this tile in the accumulator the launch adds to (accumulate_chunks' tile map:
+                         out_off is the source offset in the launch's packed sums, w * h the pixel count); the
+                         render kernels do not read it */
 };
 
 /* feature bits (scene-wide) */

@@ -275,11 +275,63 @@ __host__ __device__ inline void accumulate_pixel(const float4* partial, float4* 
   acc[i] = make_float4(sum.x, sum.y, sum.z, 0.0f);
   if constexpr (FORMAT >= 0) store_resolved<FORMAT>(out, i, sum, scale);
 }
+/* the samples of a pass's chunk c: lane.h chunk_range on the pass's schedule (the function the render kernels split
+ * a pixel's samples by), or the caller's table (hrt_debug_noise) */
+struct ChunkCounts {
+  const uint32_t* sizes; /* null: the schedule below */
+  uint32_t chunk, chunk_head, chunk_first;
+  __host__ __device__ uint32_t operator()(uint32_t c) const {
+    if (sizes) return sizes[c];
+    KParams P; /* chunk_range reads these three fields alone */
+    P.chunk = chunk;
+    P.chunk_head = chunk_head;
+    P.chunk_first = chunk_first;
+    uint32_t s0, s1;
+    chunk_range(P, c, s0, s1);
+    return s1 - s0;
+  }
+};
+/* What accumulate_chunks<FORMAT, true> takes beyond the plain kernel's arguments: the noise plane and the tile map.
+ * The map is the launch's own tile table: per launched tile out_off = the source offset in the launch's packed sums,
+ * acc_off = the destination offset in the accumulator, w * h = the pixel count, so a pass over a subset of an
+ * accumulator's tiles is one megakernel launch and this one kernel. */
+template <bool MOMENTS>
+struct MomentArgs {};
+template <>
+struct MomentArgs<true> {
+  float* m2; /* n_px f32 packed as acc (accum.h pass_moment / add_moment); null: the accumulator keeps none */
+  const G::TileDev* tiles;
+  uint32_t n_tiles;
+  ChunkCounts counts;
+};
+/* launch pixel i -> its pixel in the accumulator: the last tile whose out_off <= i */
+__host__ __device__ inline size_t mapped_pixel(const G::TileDev* tiles, uint32_t n_tiles, size_t i) {
+  uint32_t lo = 0, hi = n_tiles;
+  while (hi - lo > 1u) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (tiles[mid].out_off <= i) lo = mid;
+    else hi = mid;
+  }
+  return (size_t)tiles[lo].acc_off + (i - tiles[lo].out_off);
+}
 template <int FORMAT>
+__host__ __device__ inline void accumulate_pixel_mapped(const float4* partial, float4* acc, size_t n, uint32_t n_chunks, float scale,
+                                                        void* out, size_t i, const MomentArgs<true>& M) {
+  const size_t d = mapped_pixel(M.tiles, M.n_tiles, i);
+  const float4 a = acc[d];
+  const Vec3 sum = accum::add_pass(v3(a.x, a.y, a.z), accum::pass_sum(partial, n_chunks, n, i));
+  acc[d] = make_float4(sum.x, sum.y, sum.z, 0.0f);
+  if (M.m2) M.m2[d] = accum::add_moment(M.m2[d], accum::pass_moment(partial, n_chunks, n, i, M.counts));
+  if constexpr (FORMAT >= 0) store_resolved<FORMAT>(out, d, sum, scale);
+}
+template <int FORMAT, bool MOMENTS = false>
 __global__ __launch_bounds__(256) void accumulate_chunks(const float4* __restrict__ partial, float4* __restrict__ acc, size_t n,
-                                                         uint32_t n_chunks, float scale, void* __restrict__ out) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    accumulate_pixel<FORMAT>(partial, acc, n, n_chunks, scale, out, i);
+                                                         uint32_t n_chunks, float scale, void* __restrict__ out,
+                                                         MomentArgs<MOMENTS> M) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    if constexpr (MOMENTS) accumulate_pixel_mapped<FORMAT>(partial, acc, n, n_chunks, scale, out, i, M);
+    else accumulate_pixel<FORMAT>(partial, acc, n, n_chunks, scale, out, i);
+  }
 }
 
 /* dst += src */
@@ -290,12 +342,81 @@ __global__ __launch_bounds__(256) void accum_merge(float4* __restrict__ dst, con
     dst[i] = make_float4(sum.x, sum.y, sum.z, 0.0f);
   }
 }
+/* ... of the noise planes */
+__global__ __launch_bounds__(256) void accum_merge_m2(float* __restrict__ dst, const float* __restrict__ src, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    dst[i] = accum::add_moment(dst[i], src[i]);
+}
+
+/* One tile of an accumulator as accum_noise and accum_resolve_tiles see it: its pixels [off, off + n) of the packed
+ * order, and the scales of the samples and chunks it holds. */
+struct alignas(16) NoiseTile {
+  uint32_t off, n;
+  float inv_n;  /* accum::resolve_scale(samples) */
+  float inv_k1; /* accum::chunks_scale(chunks) */
+  uint32_t few; /* fewer than 2 chunks: no estimate */
+  uint32_t pad[3];
+};
+/* The error of every pixel of a tile (optionally stored to err, packed as acc) reduced to the tile's mean and max:
+ * one workgroup of 256 per tile, the fixed order of accum.h tile_reduce. */
+__global__ __launch_bounds__(accum::NOISE_BLOCK) void accum_noise(const float4* __restrict__ acc, const float* __restrict__ m2,
+                                                                  const NoiseTile* __restrict__ tiles, float floor,
+                                                                  float* __restrict__ err, float2* __restrict__ out) {
+  __shared__ float sh_s[accum::NOISE_BLOCK], sh_m[accum::NOISE_BLOCK];
+  const NoiseTile T = tiles[blockIdx.x];
+  const uint32_t j = threadIdx.x;
+  float s = 0.0f, m = 0.0f;
+  for (uint32_t k = j; k < T.n; k += accum::NOISE_BLOCK) {
+    const size_t d = (size_t)T.off + k;
+    const float4 a = acc[d];
+    const float e = accum::noise_err(v3(a.x, a.y, a.z), m2[d], T.inv_n, T.inv_k1, T.few != 0u, floor);
+    if (err) err[d] = e;
+    s = s + e;
+    m = accum::larger(m, e);
+  }
+  sh_s[j] = s;
+  sh_m[j] = m;
+  __syncthreads();
+  if (j < 128u) { /* s = 128, across waves */
+    s = s + sh_s[j + 128u];
+    m = accum::larger(m, sh_m[j + 128u]);
+  }
+  __syncthreads();
+  if (j < 128u) {
+    sh_s[j] = s;
+    sh_m[j] = m;
+  }
+  __syncthreads();
+  if (j < 64u) { /* s = 64 across waves, then 32 ... 1 inside wave 0: lane j takes lane j + s's value */
+    s = s + sh_s[j + 64u];
+    m = accum::larger(m, sh_m[j + 64u]);
+    for (int off = 32; off >= 1; off >>= 1) {
+      s = s + __shfl_down(s, off);
+      m = accum::larger(m, __shfl_down(m, off));
+    }
+    if (j == 0u) out[blockIdx.x] = make_float2(s * (1.0f / (float)T.n), m);
+  }
+}
 
 template <int FORMAT>
 __global__ __launch_bounds__(256) void accum_resolve(const float4* __restrict__ acc, size_t n, float scale, void* __restrict__ out) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const float4 a = acc[i];
     store_resolved<FORMAT>(out, i, v3(a.x, a.y, a.z), scale);
+  }
+}
+/* ... of an accumulator whose tiles hold different sample counts: tile t resolves with its own 1 / N_t.  A
+ * workgroup per tile (further tiles in further trips), its lanes over the tile's consecutive pixels. */
+template <int FORMAT>
+__global__ __launch_bounds__(256) void accum_resolve_tiles(const float4* __restrict__ acc, const NoiseTile* __restrict__ tiles,
+                                                           uint32_t n_tiles, void* __restrict__ out) {
+  for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    const NoiseTile T = tiles[t];
+    for (uint32_t k = threadIdx.x; k < T.n; k += blockDim.x) {
+      const size_t d = (size_t)T.off + k;
+      const float4 a = acc[d];
+      store_resolved<FORMAT>(out, d, v3(a.x, a.y, a.z), T.inv_n);
+    }
   }
 }
 
@@ -907,13 +1028,19 @@ struct SumsDest {
   int preview = -1;          /* HRT_ACCUM_* format of d_preview, -1: none */
   void* d_preview = nullptr;
   float preview_scale = 0.0f; /* 1 / the accumulator's samples after this pass */
+  /* mapped: the pass goes through accumulate_chunks' tile map (a HRT_ACCUM_NOISE accumulator, or a pass over a subset
+   * of the accumulator's tiles): launched tile i lands at pixel acc_offs[i] of the accumulator, and d_m2 (or null)
+   * takes the pass's moment */
+  bool mapped = false;
+  float* d_m2 = nullptr;
+  const uint32_t* acc_offs = nullptr;
 };
 
 template <int FORMAT>
 void launch_accumulate(const float4* partial, float4* acc, size_t n, uint32_t n_chunks, float scale, void* out,
                        hipStream_t stream) {
   hipLaunchKernelGGL((accumulate_chunks<FORMAT>), dim3(stream_blocks(n)), dim3(256), 0, stream, partial, acc, n, n_chunks,
-                     scale, out);
+                     scale, out, MomentArgs<false>{});
   hip_check(hipGetLastError(), "accumulate_chunks launch");
 }
 void launch_accumulate(int format, const float4* partial, float4* acc, size_t n, uint32_t n_chunks, float scale, void* out,
@@ -921,6 +1048,19 @@ void launch_accumulate(int format, const float4* partial, float4* acc, size_t n,
   if (format == HRT_ACCUM_F32) launch_accumulate<HRT_ACCUM_F32>(partial, acc, n, n_chunks, scale, out, stream);
   else if (format == HRT_ACCUM_RGBA8) launch_accumulate<HRT_ACCUM_RGBA8>(partial, acc, n, n_chunks, scale, out, stream);
   else launch_accumulate<-1>(partial, acc, n, n_chunks, 0.0f, nullptr, stream);
+}
+template <int FORMAT>
+void launch_accumulate_mapped(const float4* partial, float4* acc, size_t n, uint32_t n_chunks, float scale, void* out,
+                              const MomentArgs<true>& M, hipStream_t stream) {
+  hipLaunchKernelGGL((accumulate_chunks<FORMAT, true>), dim3(stream_blocks(n)), dim3(256), 0, stream, partial, acc, n, n_chunks,
+                     scale, out, M);
+  hip_check(hipGetLastError(), "accumulate_chunks launch");
+}
+void launch_accumulate_mapped(int format, const float4* partial, float4* acc, size_t n, uint32_t n_chunks, float scale, void* out,
+                              const MomentArgs<true>& M, hipStream_t stream) {
+  if (format == HRT_ACCUM_F32) launch_accumulate_mapped<HRT_ACCUM_F32>(partial, acc, n, n_chunks, scale, out, M, stream);
+  else if (format == HRT_ACCUM_RGBA8) launch_accumulate_mapped<HRT_ACCUM_RGBA8>(partial, acc, n, n_chunks, scale, out, M, stream);
+  else launch_accumulate_mapped<-1>(partial, acc, n, n_chunks, 0.0f, nullptr, M, stream);
 }
 
 /* The camera segment's leaf lists (primary_list.h), built on the launch's stream ahead of the megakernel: one
@@ -1001,7 +1141,7 @@ void render_launch(hrt_scene* s, const hrt_camera* cam, const hrt_render_params*
     if (t.w == 0 || t.h == 0 || (uint64_t)t.x + t.w > p->width || (uint64_t)t.y + t.h > p->height)
       throw HipError{HRT_ERR_INVALID_ARG, "tile outside the image"};
     uint32_t bw = (t.w + 7) / 8, bh = (t.h + 7) / 8;
-    td[i] = G::TileDev{t.x, t.y, t.w, t.h, bw, (uint32_t)pad, (uint32_t)outp, 0};
+    td[i] = G::TileDev{t.x, t.y, t.w, t.h, bw, (uint32_t)pad, (uint32_t)outp, dst.acc_offs ? dst.acc_offs[i] : (uint32_t)outp};
     pad += (uint64_t)bw * bh * 64; /* padded pixels (items: pad x n_chunks, chunk-major) */
     outp += (uint64_t)t.w * t.h;
   }
@@ -1122,7 +1262,11 @@ void render_launch(hrt_scene* s, const hrt_camera* cam, const hrt_render_params*
   else launch_any<false>(s, pl, kp, stream);
   launch_knobs(s);
   if (launched) *launched = true;
-  if (raw) {
+  if (raw && dst.mapped) {
+    const MomentArgs<true> M{dst.d_m2, kp.tiles, n_tiles, ChunkCounts{nullptr, chunk, n_head, first}};
+    launch_accumulate_mapped(dst.preview, (const float4*)sl.d_partial, dst.d_acc, (size_t)outp, n_chunks, dst.preview_scale,
+                             dst.d_preview, M, stream);
+  } else if (raw) {
     launch_accumulate(dst.preview, (const float4*)sl.d_partial, dst.d_acc, (size_t)outp, n_chunks, dst.preview_scale,
                       dst.d_preview, stream);
   } else if (n_chunks > 1) {
@@ -1225,6 +1369,20 @@ struct hrt_accum {
   FrameIdentity identity;
   std::vector<SampleRange> ranges;
   bool invalid = false; /* a pass was stopped by the walk watchdog: the sums are incomplete until a reset */
+  uint32_t flags = 0;      /* HRT_ACCUM_* creation flags */
+  float* d_m2 = nullptr;   /* HRT_ACCUM_NOISE: n_px moments (accum.h), packed as d_acc */
+  uint64_t chunks = 0;     /* K: the chunks added, of every tile while the tiles hold the same passes */
+  std::vector<uint32_t> tile_off; /* first pixel of each tile in the packed order */
+  /* Per-tile bookkeeping, non-empty only while the tiles hold DIFFERENT passes (after hrt_accum_add_tiles): tile
+   * t's sample ranges and chunks; `ranges` and `chunks` are then unused */
+  std::vector<std::vector<SampleRange>> tile_ranges;
+  std::vector<uint64_t> tile_chunks;
+  NoiseTile* d_ntiles = nullptr; /* n_tiles records for accum_noise / accum_resolve_tiles, and their host copy */
+  float2* d_nout = nullptr;      /* n_tiles x (mean, max) */
+  std::vector<NoiseTile> h_ntiles;
+  bool uniform() const { return tile_ranges.empty(); }
+  const std::vector<SampleRange>& ranges_of(size_t t) const { return uniform() ? ranges : tile_ranges[t]; }
+  uint64_t chunks_of(size_t t) const { return uniform() ? chunks : tile_chunks[t]; }
 };
 
 namespace {
@@ -1245,7 +1403,49 @@ void check_range(const std::vector<SampleRange>& have, const SampleRange& r) {
   if (r.begin >= r.end || r.end > (1ull << 32)) throw HipError{HRT_ERR_INVALID_ARG, "empty sample range, or one that ends past 2^32"};
   if (ranges_overlap(have, r)) throw HipError{HRT_ERR_INVALID_ARG, "the sample range overlaps samples the accumulator holds"};
 }
-void launch_resolve(const hrt_accum* a, int32_t format, void* d_out, hipStream_t stream) {
+void accum_uniform(const hrt_accum* a, hrt_status st, const char* what) {
+  if (!a->uniform()) throw HipError{st, what};
+}
+bool accum_empty(const hrt_accum* a) {
+  if (a->uniform()) return a->ranges.empty();
+  for (const auto& r : a->tile_ranges)
+    if (!r.empty()) return false;
+  return true;
+}
+/* the records accum_noise and accum_resolve_tiles read, from the host bookkeeping, onto the device (stream-ordered;
+ * h_ntiles stays alive with the accumulator) */
+void upload_noise_tiles(hrt_accum* a, hipStream_t stream) {
+  const size_t nt = a->tiles.size();
+  a->h_ntiles.resize(nt);
+  for (size_t t = 0; t < nt; t++) {
+    const uint64_t n = ranges_total(a->ranges_of(t)), k = a->chunks_of(t);
+    NoiseTile& T = a->h_ntiles[t];
+    memset(&T, 0, sizeof(T));
+    T.off = a->tile_off[t];
+    T.n = a->tiles[t].w * a->tiles[t].h;
+    T.inv_n = n ? accum::resolve_scale(n) : 0.0f;
+    T.few = k < 2 ? 1u : 0u;
+    T.inv_k1 = k < 2 ? 0.0f : accum::chunks_scale(k);
+  }
+  hip_check(hipMemcpyAsync(a->d_ntiles, a->h_ntiles.data(), nt * sizeof(NoiseTile), hipMemcpyHostToDevice, stream),
+            "hipMemcpyAsync(noise tiles)");
+}
+/* tiles that hold different sample counts resolve each with its own (accum_resolve_tiles); every tile needs samples */
+void launch_resolve_tiles(hrt_accum* a, int32_t format, void* d_out, hipStream_t stream) {
+  for (const auto& r : a->tile_ranges)
+    if (r.empty()) throw HipError{HRT_ERR_STATE, "a tile of the accumulator holds no samples"};
+  upload_noise_tiles(a, stream);
+  const uint32_t nt = (uint32_t)a->tiles.size(), blocks = std::min(nt, STREAM_MAX_BLOCKS);
+  if (format == HRT_ACCUM_F32)
+    hipLaunchKernelGGL((accum_resolve_tiles<HRT_ACCUM_F32>), dim3(blocks), dim3(256), 0, stream, (const float4*)a->d_acc,
+                       (const NoiseTile*)a->d_ntiles, nt, d_out);
+  else
+    hipLaunchKernelGGL((accum_resolve_tiles<HRT_ACCUM_RGBA8>), dim3(blocks), dim3(256), 0, stream, (const float4*)a->d_acc,
+                       (const NoiseTile*)a->d_ntiles, nt, d_out);
+  hip_check(hipGetLastError(), "accum_resolve_tiles launch");
+}
+void launch_resolve(hrt_accum* a, int32_t format, void* d_out, hipStream_t stream) {
+  if (!a->uniform()) return launch_resolve_tiles(a, format, d_out, stream);
   const float scale = accum::resolve_scale(ranges_total(a->ranges));
   if (format == HRT_ACCUM_F32)
     hipLaunchKernelGGL((accum_resolve<HRT_ACCUM_F32>), dim3(stream_blocks(a->n_px)), dim3(256), 0, stream, (const float4*)a->d_acc,
@@ -1256,29 +1456,115 @@ void launch_resolve(const hrt_accum* a, int32_t format, void* d_out, hipStream_t
   hip_check(hipGetLastError(), "accum_resolve launch");
 }
 
+/* K of a pass: the chunks its schedule sums a pixel's samples in */
+uint64_t pass_chunks(const hrt_scene* s, const hrt_render_params* p) {
+  uint32_t chunk = 0, n_head = 0, first = 0, n_tail = 0;
+  chunk_schedule(s, p, chunk, n_head, first, n_tail);
+  return (uint64_t)n_head + n_tail;
+}
+
 /* hrt_accum_add / hrt_accum_add_resolve: checks first (nothing changes on an error), then the shared launch */
 void accum_add(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, int32_t format, void* d_out, void* stream,
                hrt_render_stats* stats) {
   accum_usable(a);
+  if (d_out) accum_uniform(a, HRT_ERR_UNSUPPORTED, "hrt_accum_add_resolve: the accumulator's tiles hold different passes");
   const FrameIdentity id = frame_identity(cam, p);
   check_identity(a, id);
   const SampleRange r{p->sample_offset, (uint64_t)p->sample_offset + p->samples};
-  if (p->samples != 0) check_range(a->ranges, r); /* samples = 0: check_render_args reports it */
+  const size_t nt = a->tiles.size();
+  if (p->samples != 0) { /* samples = 0: check_render_args reports it */
+    if (a->uniform()) check_range(a->ranges, r);
+    else
+      for (size_t t = 0; t < nt; t++) check_range(a->tile_ranges[t], r);
+  }
   SumsDest dst;
   dst.d_acc = a->d_acc;
   dst.preview = d_out ? format : -1;
   dst.d_preview = d_out;
   dst.preview_scale = accum::resolve_scale(ranges_total(a->ranges) + p->samples);
+  dst.mapped = a->d_m2 != nullptr; /* without a noise plane: the plain kernel, as ever (the tiles map onto themselves) */
+  dst.d_m2 = a->d_m2;
   bool launched = false;
   try {
-    render_launch(a->scene, cam, p, a->tiles.data(), (uint32_t)a->tiles.size(), dst, stream, stats, &launched);
+    render_launch(a->scene, cam, p, a->tiles.data(), (uint32_t)nt, dst, stream, stats, &launched);
   } catch (...) {
     if (launched) a->invalid = true; /* the pass is (partly) in the sums and cannot be taken out again */
     throw;
   }
   a->identity = id;
   a->has_identity = true;
-  ranges_insert(a->ranges, r);
+  const uint64_t k = pass_chunks(a->scene, p);
+  if (a->uniform()) {
+    ranges_insert(a->ranges, r);
+    a->chunks += k;
+  } else {
+    for (size_t t = 0; t < nt; t++) {
+      ranges_insert(a->tile_ranges[t], r);
+      a->tile_chunks[t] += k;
+    }
+  }
+}
+
+/* hrt_accum_add_tiles: a pass over tiles[idx[0..n)] alone */
+void accum_add_tiles(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, const uint32_t* idx, uint32_t n, void* stream,
+                     hrt_render_stats* stats) {
+  accum_usable(a);
+  const size_t nt = a->tiles.size();
+  std::vector<uint8_t> taken(nt, 0);
+  for (uint32_t i = 0; i < n; i++) {
+    if (idx[i] >= nt || taken[idx[i]]) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_add_tiles: a tile index out of range or given twice"};
+    taken[idx[i]] = 1;
+  }
+  const FrameIdentity id = frame_identity(cam, p);
+  check_identity(a, id);
+  const SampleRange r{p->sample_offset, (uint64_t)p->sample_offset + p->samples};
+  if (p->samples != 0)
+    for (uint32_t i = 0; i < n; i++) check_range(a->ranges_of(idx[i]), r);
+  std::vector<hrt_tile> sub(n);
+  std::vector<uint32_t> offs(n);
+  for (uint32_t i = 0; i < n; i++) {
+    sub[i] = a->tiles[idx[i]];
+    offs[i] = a->tile_off[idx[i]];
+  }
+  SumsDest dst;
+  dst.d_acc = a->d_acc;
+  dst.mapped = true;
+  dst.d_m2 = a->d_m2;
+  dst.acc_offs = offs.data();
+  bool launched = false;
+  try {
+    render_launch(a->scene, cam, p, sub.data(), n, dst, stream, stats, &launched);
+  } catch (...) {
+    if (launched) a->invalid = true;
+    throw;
+  }
+  a->identity = id;
+  a->has_identity = true;
+  const uint64_t k = pass_chunks(a->scene, p);
+  if (a->uniform()) {
+    a->tile_ranges.assign(nt, a->ranges);
+    a->tile_chunks.assign(nt, a->chunks);
+  }
+  for (uint32_t i = 0; i < n; i++) {
+    ranges_insert(a->tile_ranges[idx[i]], r);
+    a->tile_chunks[idx[i]] += k;
+  }
+  /* every tile holds the same passes again (e.g. the pass went to all of them): back to the uniform bookkeeping */
+  bool same = true;
+  for (size_t t = 1; t < nt && same; t++) {
+    const auto &x = a->tile_ranges[0], &y = a->tile_ranges[t];
+    same = a->tile_chunks[t] == a->tile_chunks[0] && x.size() == y.size() &&
+           (x.empty() || memcmp(x.data(), y.data(), x.size() * sizeof(SampleRange)) == 0);
+  }
+  if (same) {
+    a->ranges = a->tile_ranges[0];
+    a->chunks = a->tile_chunks[0];
+    a->tile_ranges.clear();
+    a->tile_chunks.clear();
+  } else {
+    a->ranges.clear();
+    a->chunks = 0;
+  }
 }
 
 }  // namespace
@@ -1511,9 +1797,15 @@ hrt_status hrt_debug_box_test(int32_t form, int32_t on_device, const float* boxe
 /* ---------------------------------------------------------------------------- sample accumulation */
 hrt_status hrt_accum_create(hrt_scene* s, uint32_t width, uint32_t height, const hrt_tile* tiles, uint32_t n_tiles,
                             hrt_accum** out) {
+  return hrt_accum_create_ex(s, width, height, tiles, n_tiles, 0, out);
+}
+
+hrt_status hrt_accum_create_ex(hrt_scene* s, uint32_t width, uint32_t height, const hrt_tile* tiles, uint32_t n_tiles,
+                               uint32_t flags, hrt_accum** out) {
   return hguard([&] {
     if (!s || !tiles || !out || n_tiles == 0) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_create: null argument or no tiles"};
     *out = nullptr;
+    if (flags & ~(uint32_t)HRT_ACCUM_NOISE) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_create_ex: unknown flag"};
     if (width < 2 || height < 2 || width > 65535 || height > 65535)
       throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_create: 2 <= width, height <= 65535"};
     uint64_t n_px = 0;
@@ -1533,11 +1825,26 @@ hrt_status hrt_accum_create(hrt_scene* s, uint32_t width, uint32_t height, const
     a->height = height;
     a->tiles.assign(tiles, tiles + n_tiles);
     a->n_px = (size_t)n_px;
+    a->flags = flags;
+    a->tile_off.resize(n_tiles);
+    for (uint32_t i = 0, off = 0; i < n_tiles; i++) {
+      a->tile_off[i] = off;
+      off += tiles[i].w * tiles[i].h;
+    }
     try {
       hip_check(hipMalloc((void**)&a->d_acc, a->n_px * sizeof(float4)), "hipMalloc(accumulator)");
       hip_check(hipMemset(a->d_acc, 0, a->n_px * sizeof(float4)), "hipMemset(accumulator)");
+      hip_check(hipMalloc((void**)&a->d_ntiles, n_tiles * sizeof(NoiseTile)), "hipMalloc(accumulator tiles)");
+      if (flags & HRT_ACCUM_NOISE) {
+        hip_check(hipMalloc((void**)&a->d_m2, a->n_px * sizeof(float)), "hipMalloc(noise plane)");
+        hip_check(hipMemset(a->d_m2, 0, a->n_px * sizeof(float)), "hipMemset(noise plane)");
+        hip_check(hipMalloc((void**)&a->d_nout, n_tiles * sizeof(float2)), "hipMalloc(noise records)");
+      }
     } catch (...) {
       if (a->d_acc) (void)hipFree(a->d_acc);
+      if (a->d_ntiles) (void)hipFree(a->d_ntiles);
+      if (a->d_m2) (void)hipFree(a->d_m2);
+      if (a->d_nout) (void)hipFree(a->d_nout);
       delete a;
       throw;
     }
@@ -1551,6 +1858,9 @@ void hrt_accum_destroy(hrt_accum* a) {
   (void)hipGetDevice(&prev);
   (void)hipSetDevice(a->device);
   if (a->d_acc) (void)hipFree(a->d_acc); /* waits for the work that uses it */
+  if (a->d_m2) (void)hipFree(a->d_m2);
+  if (a->d_ntiles) (void)hipFree(a->d_ntiles);
+  if (a->d_nout) (void)hipFree(a->d_nout);
   if (prev >= 0) (void)hipSetDevice(prev);
   delete a;
 }
@@ -1560,7 +1870,11 @@ hrt_status hrt_accum_reset(hrt_accum* a, void* stream) {
     if (!a) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_reset: null accumulator"};
     DeviceGuard dg(a->device);
     hip_check(hipMemsetAsync(a->d_acc, 0, a->n_px * sizeof(float4), (hipStream_t)stream), "hipMemsetAsync(accumulator)");
+    if (a->d_m2) hip_check(hipMemsetAsync(a->d_m2, 0, a->n_px * sizeof(float), (hipStream_t)stream), "hipMemsetAsync(noise plane)");
     a->ranges.clear();
+    a->chunks = 0;
+    a->tile_ranges.clear();
+    a->tile_chunks.clear();
     a->has_identity = false;
     a->invalid = false;
   });
@@ -1586,7 +1900,59 @@ hrt_status hrt_accum_add_resolve(hrt_accum* a, const hrt_camera* cam, const hrt_
 hrt_status hrt_accum_samples(const hrt_accum* a, uint64_t* samples) {
   return hguard([&] {
     if (!a || !samples) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_samples: null argument"};
+    accum_uniform(a, HRT_ERR_STATE, "hrt_accum_samples: the accumulator's tiles hold different passes (hrt_accum_tile_samples)");
     *samples = ranges_total(a->ranges);
+  });
+}
+
+hrt_status hrt_accum_tile_samples(const hrt_accum* a, uint64_t* per_tile) {
+  return hguard([&] {
+    if (!a || !per_tile) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_tile_samples: null argument"};
+    for (size_t t = 0; t < a->tiles.size(); t++) per_tile[t] = ranges_total(a->ranges_of(t));
+  });
+}
+
+hrt_status hrt_accum_add_tiles(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, const uint32_t* idx, uint32_t n,
+                               void* stream, hrt_render_stats* stats) {
+  return hguard([&] {
+    if (!a || !cam || !p || !idx || n == 0) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_add_tiles: null argument or no tiles"};
+    accum_add_tiles(a, cam, p, idx, n, stream, stats);
+  });
+}
+
+hrt_status hrt_accum_noise(hrt_accum* a, float floor, float* d_err, void* stream_, hrt_tile_noise* tiles_out) {
+  return hguard([&] {
+    if (!a || !tiles_out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_noise: null argument"};
+    if (!(floor > 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_noise: floor must be > 0"};
+    accum_usable(a);
+    if (!a->d_m2) throw HipError{HRT_ERR_STATE, "hrt_accum_noise: the accumulator was created without HRT_ACCUM_NOISE"};
+    if (accum_empty(a)) throw HipError{HRT_ERR_STATE, "the accumulator holds no samples"};
+    DeviceGuard dg(a->device);
+    hipStream_t stream = (hipStream_t)stream_;
+    const uint32_t nt = (uint32_t)a->tiles.size();
+    upload_noise_tiles(a, stream);
+    hipLaunchKernelGGL(accum_noise, dim3(nt), dim3(accum::NOISE_BLOCK), 0, stream, (const float4*)a->d_acc, (const float*)a->d_m2,
+                       (const NoiseTile*)a->d_ntiles, floor, d_err, a->d_nout);
+    hip_check(hipGetLastError(), "accum_noise launch");
+    std::vector<float2> rec(nt);
+    hip_check(hipMemcpyAsync(rec.data(), a->d_nout, nt * sizeof(float2), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(noise records)");
+    hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize(noise)");
+    for (uint32_t t = 0; t < nt; t++) {
+      tiles_out[t].mean = rec[t].x;
+      tiles_out[t].max = rec[t].y;
+      tiles_out[t].samples = ranges_total(a->ranges_of(t));
+      tiles_out[t].chunks = a->chunks_of(t);
+    }
+  });
+}
+
+hrt_status hrt_debug_accum_moments(hrt_accum* a, float* m2_out) {
+  return hguard([&] {
+    if (!a || !m2_out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_accum_moments: null argument"};
+    if (!a->d_m2) throw HipError{HRT_ERR_STATE, "hrt_debug_accum_moments: the accumulator was created without HRT_ACCUM_NOISE"};
+    DeviceGuard dg(a->device);
+    hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    hip_check(hipMemcpy(m2_out, a->d_m2, a->n_px * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(moments)");
   });
 }
 
@@ -1595,7 +1961,7 @@ hrt_status hrt_accum_resolve(hrt_accum* a, int32_t format, void* d_out, void* st
     if (!a || !d_out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_resolve: null argument"};
     accum_format(format);
     accum_usable(a);
-    if (a->ranges.empty()) throw HipError{HRT_ERR_STATE, "the accumulator holds no samples"};
+    if (accum_empty(a)) throw HipError{HRT_ERR_STATE, "the accumulator holds no samples"};
     DeviceGuard dg(a->device);
     launch_resolve(a, format, d_out, (hipStream_t)stream);
   });
@@ -1607,7 +1973,7 @@ hrt_status hrt_accum_resolve_host(hrt_accum* a, int32_t format, void* out) {
     if (!a || !out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_resolve_host: null argument"};
     accum_format(format);
     accum_usable(a);
-    if (a->ranges.empty()) throw HipError{HRT_ERR_STATE, "the accumulator holds no samples"};
+    if (accum_empty(a)) throw HipError{HRT_ERR_STATE, "the accumulator holds no samples"};
     DeviceGuard dg(a->device);
     const size_t bytes = a->n_px * (format == HRT_ACCUM_F32 ? 16u : 4u);
     buf = out_pool_take(a->scene, a->n_px * 16 + 16);
@@ -1624,6 +1990,10 @@ hrt_status hrt_accum_merge(hrt_accum* dst, const hrt_accum* src, void* stream) {
     if (!dst || !src || dst == src) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_merge: null argument, or an accumulator into itself"};
     accum_usable(dst);
     accum_usable(src);
+    if ((dst->d_m2 != nullptr) != (src->d_m2 != nullptr))
+      throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_merge: one accumulator keeps a noise plane (HRT_ACCUM_NOISE), the other none"};
+    accum_uniform(dst, HRT_ERR_UNSUPPORTED, "hrt_accum_merge: the accumulator's tiles hold different passes");
+    accum_uniform(src, HRT_ERR_UNSUPPORTED, "hrt_accum_merge: the accumulator's tiles hold different passes");
     if (dst->device != src->device || dst->width != src->width || dst->height != src->height ||
         dst->tiles.size() != src->tiles.size() ||
         memcmp(dst->tiles.data(), src->tiles.data(), dst->tiles.size() * sizeof(hrt_tile)) != 0)
@@ -1635,6 +2005,12 @@ hrt_status hrt_accum_merge(hrt_accum* dst, const hrt_accum* src, void* stream) {
     hipLaunchKernelGGL(accum_merge, dim3(stream_blocks(dst->n_px)), dim3(256), 0, (hipStream_t)stream, dst->d_acc,
                        (const float4*)src->d_acc, dst->n_px);
     hip_check(hipGetLastError(), "accum_merge launch");
+    if (dst->d_m2) {
+      hipLaunchKernelGGL(accum_merge_m2, dim3(stream_blocks(dst->n_px)), dim3(256), 0, (hipStream_t)stream, dst->d_m2,
+                         (const float*)src->d_m2, dst->n_px);
+      hip_check(hipGetLastError(), "accum_merge_m2 launch");
+    }
+    dst->chunks += src->chunks;
     dst->identity = src->identity;
     dst->has_identity = true;
     for (const SampleRange& r : src->ranges) ranges_insert(dst->ranges, r);
@@ -1645,6 +2021,7 @@ hrt_status hrt_accum_download(hrt_accum* a, float* sums, uint32_t* ranges, uint3
   return hguard([&] {
     if (!a || !n_ranges) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_download: null argument"};
     accum_usable(a);
+    accum_uniform(a, HRT_ERR_UNSUPPORTED, "hrt_accum_download: the accumulator's tiles hold different passes");
     *n_ranges = (uint32_t)a->ranges.size();
     if (!sums || cap < a->ranges.size()) return;
     if (!ranges && !a->ranges.empty()) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_download: null ranges"};
@@ -1663,6 +2040,8 @@ hrt_status hrt_accum_upload(hrt_accum* a, const hrt_camera* cam, const hrt_rende
   return hguard([&] {
     if (!a || !cam || !p || !sums || (!ranges && n_ranges)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_upload: null argument"};
     accum_usable(a);
+    if (a->d_m2) throw HipError{HRT_ERR_UNSUPPORTED, "hrt_accum_upload: the noise plane of a HRT_ACCUM_NOISE accumulator does not travel"};
+    accum_uniform(a, HRT_ERR_UNSUPPORTED, "hrt_accum_upload: the accumulator's tiles hold different passes");
     const FrameIdentity id = frame_identity(cam, p);
     check_identity(a, id);
     /* the ranges must be addable one after the other: checked on a copy, so an error changes nothing */
@@ -1730,6 +2109,59 @@ hrt_status hrt_debug_accumulate(int32_t on_device, const float* partial, uint32_
     hip_check(hipMemcpy(second.data(), d_out2.p, out_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
     if (memcmp(out, second.data(), out_bytes) != 0)
       throw HipError{HRT_ERR_STATE, "hrt_debug_accumulate: accumulate_chunks' fused resolve and accum_resolve differ"};
+  });
+}
+
+hrt_status hrt_debug_noise(int32_t on_device, const float* partial, const uint32_t* sizes, uint32_t n_chunks, uint32_t n,
+                           float* acc_inout, float* m2_inout, uint64_t samples, uint64_t chunks, float floor, float* err_out,
+                           float* mean_max_out) {
+  return hguard([&] {
+    if (!partial || !sizes || !acc_inout || !m2_inout || !err_out || !mean_max_out || n_chunks == 0 || n == 0 || samples == 0 ||
+        samples > (1ull << 32))
+      throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_noise: bad argument"};
+    for (uint32_t c = 0; c < n_chunks; c++)
+      if (sizes[c] == 0) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_noise: an empty chunk"};
+    if (!(floor > 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_noise: floor must be > 0"};
+    NoiseTile T;
+    memset(&T, 0, sizeof(T));
+    T.n = n;
+    T.inv_n = accum::resolve_scale(samples);
+    T.few = chunks < 2 ? 1u : 0u;
+    T.inv_k1 = chunks < 2 ? 0.0f : accum::chunks_scale(chunks);
+    const G::TileDev map{0, 0, n, 1, (n + 7) / 8, 0, 0, 0}; /* one tile: the launch's pixels onto themselves */
+    if (!on_device) {
+      const float4* hp = reinterpret_cast<const float4*>(partial);
+      float4* ha = reinterpret_cast<float4*>(acc_inout);
+      const MomentArgs<true> M{m2_inout, &map, 1u, ChunkCounts{sizes, 0, 0, 0}};
+      for (size_t i = 0; i < n; i++) accumulate_pixel_mapped<-1>(hp, ha, n, n_chunks, 0.0f, nullptr, i, M);
+      for (size_t i = 0; i < n; i++)
+        err_out[i] = accum::noise_err(v3(ha[i].x, ha[i].y, ha[i].z), m2_inout[i], T.inv_n, T.inv_k1, T.few != 0u, floor);
+      accum::tile_reduce(err_out, n, mean_max_out[0], mean_max_out[1]);
+      return;
+    }
+    /* the real kernels on the calling thread's current device */
+    const size_t p_bytes = (size_t)n_chunks * n * sizeof(float4), a_bytes = (size_t)n * sizeof(float4), m_bytes = (size_t)n * sizeof(float);
+    DevBuf<float4> d_partial(p_bytes), d_acc(a_bytes);
+    DevBuf<float> d_m2(m_bytes), d_err(m_bytes);
+    DevBuf<uint32_t> d_sizes(n_chunks * sizeof(uint32_t));
+    DevBuf<G::TileDev> d_map(sizeof(G::TileDev));
+    DevBuf<NoiseTile> d_tile(sizeof(NoiseTile));
+    DevBuf<float2> d_rec(sizeof(float2));
+    hip_check(hipMemcpy(d_partial.p, partial, p_bytes, hipMemcpyHostToDevice), "hipMemcpy");
+    hip_check(hipMemcpy(d_acc.p, acc_inout, a_bytes, hipMemcpyHostToDevice), "hipMemcpy");
+    hip_check(hipMemcpy(d_m2.p, m2_inout, m_bytes, hipMemcpyHostToDevice), "hipMemcpy");
+    hip_check(hipMemcpy(d_sizes.p, sizes, n_chunks * sizeof(uint32_t), hipMemcpyHostToDevice), "hipMemcpy");
+    hip_check(hipMemcpy(d_map.p, &map, sizeof(map), hipMemcpyHostToDevice), "hipMemcpy");
+    hip_check(hipMemcpy(d_tile.p, &T, sizeof(T), hipMemcpyHostToDevice), "hipMemcpy");
+    const MomentArgs<true> M{d_m2.p, d_map.p, 1u, ChunkCounts{d_sizes.p, 0, 0, 0}};
+    launch_accumulate_mapped(-1, d_partial.p, d_acc.p, n, n_chunks, 0.0f, nullptr, M, nullptr);
+    hipLaunchKernelGGL(accum_noise, dim3(1), dim3(accum::NOISE_BLOCK), 0, nullptr, (const float4*)d_acc.p, (const float*)d_m2.p,
+                       (const NoiseTile*)d_tile.p, floor, d_err.p, d_rec.p);
+    hip_check(hipGetLastError(), "accum_noise launch");
+    hip_check(hipMemcpy(acc_inout, d_acc.p, a_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+    hip_check(hipMemcpy(m2_inout, d_m2.p, m_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+    hip_check(hipMemcpy(err_out, d_err.p, m_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+    hip_check(hipMemcpy(mean_max_out, d_rec.p, sizeof(float2), hipMemcpyDeviceToHost), "hipMemcpy");
   });
 }
 

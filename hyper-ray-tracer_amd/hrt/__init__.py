@@ -143,6 +143,11 @@ class LaunchInfo(ctypes.Structure):
     ] + [("knobs", ctypes.c_char * 256)]
 
 
+class TileNoise(ctypes.Structure):
+    """hrt_tile_noise: a tile's mean and max per-pixel error, and the samples and chunks it holds."""
+    _fields_ = [("mean", ctypes.c_float), ("max", ctypes.c_float), ("samples", ctypes.c_uint64), ("chunks", ctypes.c_uint64)]
+
+
 class SceneOptions(ctypes.Structure):
     """hrt_scene_options: the explicit configuration that can change an image's bits (all-zero = default)."""
     _fields_ = [(n, ctypes.c_uint32) for n in ("bvh_ties", "walk_tree", "chunk_min", "chunk_max", "chunk_uniform")]
@@ -153,7 +158,9 @@ OPTIONAL = {"hrt_abi_version", "hrt_last_launch", "hrt_debug_box_test", "hrt_sce
             "hrt_debug_sample_chunks", "hrt_scene_set_view",
             "hrt_accum_create", "hrt_accum_destroy", "hrt_accum_reset", "hrt_accum_add", "hrt_accum_add_resolve",
             "hrt_accum_samples", "hrt_accum_resolve", "hrt_accum_resolve_host", "hrt_accum_merge", "hrt_accum_download",
-            "hrt_accum_upload", "hrt_debug_accumulate", "hrt_debug_walk_regroup"}
+            "hrt_accum_upload", "hrt_debug_accumulate", "hrt_debug_walk_regroup",
+            "hrt_accum_create_ex", "hrt_accum_add_tiles", "hrt_accum_noise", "hrt_accum_tile_samples", "hrt_debug_noise",
+            "hrt_debug_accum_moments"}
 HRT_LIB_OVERRIDE = bool(os.environ.get("HRT_LIB"))
 
 # Every entry point of include/hrt/hrt.h (tests/test_abi.py checks the header against this list).
@@ -171,6 +178,8 @@ EXPORTS = [
     "hrt_accum_create", "hrt_accum_destroy", "hrt_accum_reset", "hrt_accum_add", "hrt_accum_add_resolve", "hrt_accum_samples",
     "hrt_accum_resolve", "hrt_accum_resolve_host", "hrt_accum_merge", "hrt_accum_download", "hrt_accum_upload",
     "hrt_debug_accumulate", "hrt_debug_walk_regroup",
+    "hrt_accum_create_ex", "hrt_accum_add_tiles", "hrt_accum_noise", "hrt_accum_tile_samples", "hrt_debug_noise",
+    "hrt_debug_accum_moments",
 ]
 
 ABI_VERSION = 6  # include/hrt/hrt.h HRT_ABI_VERSION: the struct layouts below
@@ -263,6 +272,13 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "hrt_accum_upload": (S, [vp, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams), vp, vp, u32]),
         "hrt_debug_accumulate": (S, [i32, vp, u32, u32, vp, u64, i32, vp]),
         "hrt_debug_walk_regroup": (S, [i32, vp, u32, u32, vp, vp, vp, vp]),
+        "hrt_accum_create_ex": (S, [vp, u32, u32, vp, u32, u32, ctypes.POINTER(vp)]),
+        "hrt_accum_add_tiles": (S, [vp, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams), vp, u32, vp,
+                                    ctypes.POINTER(RenderStats)]),
+        "hrt_accum_noise": (S, [vp, f, vp, vp, vp]),
+        "hrt_accum_tile_samples": (S, [vp, vp]),
+        "hrt_debug_noise": (S, [i32, vp, vp, u32, u32, vp, vp, u64, u64, f, vp, vp]),
+        "hrt_debug_accum_moments": (S, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         if name in OPTIONAL and HRT_LIB_OVERRIDE and not hasattr(L, name):
@@ -536,22 +552,29 @@ def render_tiles_device(scene: Scene, cam: Camera, p: RenderParams, tiles, d_out
 
 
 ACCUM_F32, ACCUM_RGBA8 = 0, 1
+ACCUM_NOISE = 1  # hrt_accum_create_ex flag
 _ACCUM_FORMATS = {"f32": ACCUM_F32, "rgba8": ACCUM_RGBA8}
 
 
 class Accumulator:
     """hrt_accum: device-resident raw per-pixel sums of a tile set (the whole frame when `tiles` is None).  Passes
     add sample ranges (`add` with params.sample_offset / params.samples), and `resolve` gives the frame of the
-    samples held so far.  The frame's bits depend on the pass schedule alone (include/hrt/hrt.h)."""
+    samples held so far.  The frame's bits depend on the pass schedule alone (include/hrt/hrt.h).  noise=True
+    (HRT_ACCUM_NOISE) also keeps the noise plane that `noise` and `refine` read."""
 
-    def __init__(self, scene: Scene, width: int, height: int, tiles=None):
+    def __init__(self, scene: Scene, width: int, height: int, tiles=None, noise: bool = False):
         self.scene, self.width, self.height = scene, int(width), int(height)  # the scene must outlive the accumulator
         self.tiles = [tuple(int(v) for v in t) for t in tiles] if tiles is not None else [(0, 0, self.width, self.height)]
         self.n_pixels = sum(t[2] * t[3] for t in self.tiles)
         self.h = ctypes.c_void_p()
         arr = (Tile * max(1, len(self.tiles)))(*[Tile(*t) for t in self.tiles])
-        _check(load().hrt_accum_create(scene.h, self.width, self.height, ctypes.cast(arr, ctypes.c_void_p), len(self.tiles),
-                                       ctypes.byref(self.h)))
+        self.has_noise = bool(noise)
+        if noise:
+            _check(load().hrt_accum_create_ex(scene.h, self.width, self.height, ctypes.cast(arr, ctypes.c_void_p),
+                                              len(self.tiles), ACCUM_NOISE, ctypes.byref(self.h)))
+        else:
+            _check(load().hrt_accum_create(scene.h, self.width, self.height, ctypes.cast(arr, ctypes.c_void_p),
+                                           len(self.tiles), ctypes.byref(self.h)))
 
     def close(self):
         if self.h:
@@ -570,12 +593,20 @@ class Accumulator:
             return flat.reshape(self.tiles[0][3], self.tiles[0][2], 4)
         return flat.reshape(self.n_pixels, 4)
 
-    def add(self, cam: Camera, p: RenderParams, stats: bool = False, preview=None):
+    def add(self, cam: Camera, p: RenderParams, stats: bool = False, preview=None, tiles=None):
         """Render samples [p.sample_offset, p.sample_offset + p.samples) of every pixel and add them.  preview
         ("f32" / "rgba8", or True for "f32"): also return the frame after this pass, resolved by the kernel that adds
-        the pass (hrt_accum_add_resolve).  Returns None, RenderStats, the preview, or (preview, RenderStats)."""
+        the pass (hrt_accum_add_resolve).  tiles: indices into self.tiles; the pass then goes to those tiles alone
+        (hrt_accum_add_tiles; no preview).  Returns None, RenderStats, the preview, or (preview, RenderStats)."""
         st = RenderStats()
         sp = ctypes.byref(st) if stats else None
+        if tiles is not None:
+            if preview is not None and preview is not False:
+                raise ValueError("a pass over a subset of the tiles has no preview")
+            idx = np.ascontiguousarray(list(tiles), np.uint32)
+            _check(load().hrt_accum_add_tiles(self.h, ctypes.byref(cam), ctypes.byref(p), idx.ctypes.data if idx.size else None,
+                                              idx.size, None, sp))
+            return st if stats else None
         if preview is None or preview is False:
             _check(load().hrt_accum_add(self.h, ctypes.byref(cam), ctypes.byref(p), None, sp))
             return st if stats else None
@@ -596,6 +627,65 @@ class Accumulator:
         n = ctypes.c_uint64()
         _check(load().hrt_accum_samples(self.h, ctypes.byref(n)))
         return n.value
+
+    @property
+    def tile_samples(self) -> List[int]:
+        """The samples each tile holds (hrt_accum_tile_samples)."""
+        n = np.zeros(len(self.tiles), np.uint64)
+        _check(load().hrt_accum_tile_samples(self.h, n.ctypes.data))
+        return [int(v) for v in n]
+
+    def noise(self, floor: float = 0.05, error_map: bool = False):
+        """hrt_accum_noise: one TileNoise per tile (mean and max of the per-pixel relative standard error, samples,
+        chunks); with error_map also the per-pixel errors as float32 (n_pixels,), packed as the tiles are."""
+        rec = (TileNoise * len(self.tiles))()
+        if not error_map:
+            _check(load().hrt_accum_noise(self.h, float(floor), None, None, ctypes.cast(rec, ctypes.c_void_p)))
+            return list(rec)
+        import torch
+
+        dev = torch.device("cuda", self.scene.device if self.scene.device >= 0 else torch.cuda.current_device())
+        buf = torch.empty(self.n_pixels, dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        _check(load().hrt_accum_noise(self.h, float(floor), ctypes.c_void_p(buf.data_ptr()), ctypes.c_void_p(stream.cuda_stream),
+                                      ctypes.cast(rec, ctypes.c_void_p)))
+        return list(rec), buf.cpu().numpy()
+
+    def moments(self) -> np.ndarray:
+        """The noise plane m2 as float32 (n_pixels,) (hrt_debug_accum_moments)."""
+        out = np.zeros(self.n_pixels, np.float32)
+        _check(load().hrt_debug_accum_moments(self.h, out.ctypes.data))
+        return out
+
+    def refine(self, cam: Camera, p: RenderParams, target: float, pass_spp: int, max_spp: int, floor: float = 0.05,
+               min_spp: int = 0, on_pass=None):
+        """Noise-driven passes of pass_spp samples (p's samples and sample_offset are ignored): one pass over every
+        tile, then passes over the tiles whose mean error exceeds `target` (or that hold fewer than min_spp samples)
+        and whose samples have not reached max_spp, until no such tile is left.  A tile's k-th pass is always samples
+        [k * pass_spp, (k + 1) * pass_spp), so its pixels depend on its pass count alone.  on_pass(tile indices,
+        records) is called after every pass.  Returns the per-tile records (noise(floor))."""
+        q = RenderParams.from_buffer_copy(p)
+        q.samples = int(pass_spp)
+        todo = list(range(len(self.tiles)))
+        first = True
+        while True:
+            held = self.tile_samples
+            if first:
+                if len(set(held)) != 1:
+                    raise ValueError("refine starts from an accumulator whose tiles hold the same passes")
+                q.sample_offset = held[0]
+                self.add(cam, q)
+                first = False
+            else:
+                # tiles in `todo` are those that took every pass so far, so they all hold the same samples
+                q.sample_offset = held[todo[0]]
+                self.add(cam, q, tiles=todo)
+            rec = self.noise(floor)
+            if on_pass is not None:
+                on_pass(todo, rec)
+            todo = [t for t in todo if (rec[t].mean > target or rec[t].samples < min_spp) and rec[t].samples < max_spp]
+            if not todo:
+                return rec
 
     def resolve(self, fmt: str = "f32") -> np.ndarray:
         """The frame of the samples held: float32 sqrt(sum / samples) with alpha 1 shaped like hrt.render's result,
@@ -641,6 +731,25 @@ def debug_accumulate(partial: np.ndarray, acc: np.ndarray, samples: int = 0, fmt
     _check(load().hrt_debug_accumulate(1 if on_device else 0, pa.ctypes.data, n_chunks, n, a.ctypes.data, int(samples),
                                        -1 if fmt is None else _ACCUM_FORMATS[fmt], None if out is None else out.ctypes.data))
     return a, out
+
+
+def debug_noise(partial: np.ndarray, sizes, acc: np.ndarray, m2: np.ndarray, samples: int, chunks: int, floor: float = 0.05,
+                on_device: bool = False):
+    """hrt_debug_noise: the noise estimate of csrc/accum.h for one tile of n pixels on the host, or through the real
+    kernels on the current device.  partial: (n_chunks, n, 4) float32 chunk sums of one pass with `sizes` samples
+    each, acc (n, 4) / m2 (n,) the sums and moments before it, samples / chunks: N and K held after it.  Returns
+    (acc, m2 after the pass, err (n,), mean, max) as float32."""
+    pa = np.ascontiguousarray(partial, np.float32)
+    n_chunks, n = pa.shape[0], pa.shape[1]
+    sz = np.ascontiguousarray(sizes, np.uint32)
+    if sz.shape != (n_chunks,):
+        raise ValueError("one size per chunk")
+    a = np.array(acc, np.float32).reshape(n, 4).copy()
+    m = np.array(m2, np.float32).reshape(n).copy()
+    err, mm = np.zeros(n, np.float32), np.zeros(2, np.float32)
+    _check(load().hrt_debug_noise(1 if on_device else 0, pa.ctypes.data, sz.ctypes.data, n_chunks, n, a.ctypes.data, m.ctypes.data,
+                                  int(samples), int(chunks), float(floor), err.ctypes.data, mm.ctypes.data))
+    return a, m, err, mm[0], mm[1]
 
 
 WALK_GREEDY, WALK_DP_AREA, WALK_DP_LEAVES, WALK_GREEDY_SUB, WALK_DEVICE = range(5)

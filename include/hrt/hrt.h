@@ -337,6 +337,12 @@ enum {
  * samples.  The scene must be committed (HRT_ERR_STATE); the accumulator lives on the scene's device. */
 hrt_status hrt_accum_create(hrt_scene* s, uint32_t width, uint32_t height, const hrt_tile* tiles, uint32_t n_tiles,
                             hrt_accum** out);
+/* hrt_accum_create with flags (0: hrt_accum_create itself) */
+enum {
+  HRT_ACCUM_NOISE = 1 /* also keep the noise plane (f32 per pixel) that hrt_accum_noise reads: see below */
+};
+hrt_status hrt_accum_create_ex(hrt_scene* s, uint32_t width, uint32_t height, const hrt_tile* tiles, uint32_t n_tiles,
+                               uint32_t flags, hrt_accum** out);
 void hrt_accum_destroy(hrt_accum* a);
 hrt_status hrt_accum_reset(hrt_accum* a, void* stream);
 /* Render samples [p->sample_offset, p->sample_offset + p->samples) of every pixel and add them.  stats: the
@@ -364,6 +370,61 @@ hrt_status hrt_accum_merge(hrt_accum* dst, const hrt_accum* src, void* stream);
 hrt_status hrt_accum_download(hrt_accum* a, float* sums, uint32_t* ranges, uint32_t cap, uint32_t* n_ranges);
 hrt_status hrt_accum_upload(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, const float* sums,
                             const uint32_t* ranges, uint32_t n_ranges);
+
+/* ---- noise estimate and passes over a subset of the tiles ----
+ * A HRT_ACCUM_NOISE accumulator keeps, beside the sums, the moment m2 of every pixel; hrt_accum_noise turns it into
+ * the relative standard error of each pixel's mean and a mean / max of that per tile, and hrt_accum_add_tiles sends
+ * a further pass to chosen tiles alone.  The library holds the mechanism only: which tiles get another pass is the
+ * caller's policy (examples/render_adaptive.c, Python Accumulator.refine).
+ *
+ * THE BIT CONTRACT of the noise plane and the error (csrc/accum.h, -ffp-contract=off, all in f32):
+ *   - a sum's value is luma(s) = (s.x + s.y) + s.z; Y_c is a chunk sum's value and n_c the chunk's sample count in
+ *     the pass's schedule (hrt_debug_sample_chunks);
+ *   - a pass's moment is the terms (Y_c * Y_c) * (1.0f / (float)n_c) added in chunk order starting from chunk 0's,
+ *     and the plane takes it as ONE addend, m2 = m2 + pass_moment; hrt_accum_merge does dst.m2 + src.m2;
+ *   - a tile keeps the sample ranges it holds (N samples) and K, the number of chunks added to it;
+ *   - with Y = luma(acc): var = max((m2 - (Y * Y) * (1 / N)) * (1 / (K - 1)), 0) and
+ *     err = sqrtf(var * (1 / N)) / max(Y * (1 / N), floor); K < 2 gives +inf.  floor > 0 is the caller's, in units of
+ *     the mean of Y: darker pixels are measured against it (a black pixel's error is 0);
+ *   - a tile's mean and max: thread j of 256 folds the errors of pixels j, j + 256, ... of the tile's packed order,
+ *     in order, from 0; then x[j] = x[j] (op) x[j + s] for s = 128 ... 1; mean = x[0] * (1.0f / (float)pixels).
+ *     +inf propagates into both.
+ * var is the weighted batch-means estimate of one sample's variance (unbiased for chunks of unequal sizes), so err
+ * estimates the relative standard error of the pixel's mean.  In f32 it bottoms out near 2e-4: below
+ * that a pixel is converged, not measured.
+ * Subset passes: for each selected tile's pixels the pass sum is exactly hrt_render's for those params, followed by
+ * acc + pass_sum (and m2 + pass_moment).  A tile's pixels and its noise plane are a function of THAT TILE's pass
+ * schedule alone: never of which other tiles took part in a pass, of the tile split or of the device.  Each tile
+ * resolves with its own sample count.
+ * While the tiles hold different passes: hrt_accum_samples is HRT_ERR_STATE (hrt_accum_tile_samples answers);
+ * hrt_accum_add is allowed and its range is checked against every tile; hrt_accum_add_resolve, merge, download and
+ * upload are HRT_ERR_UNSUPPORTED; a resolve needs samples in every tile (HRT_ERR_STATE).  Once every tile holds the
+ * same ranges and chunk count again, the accumulator is an ordinary one again.
+ * HRT_ACCUM_NOISE accumulators otherwise behave as plain ones (same sums, same frames, bit for bit) except: merge
+ * needs both sides to have the flag (HRT_ERR_INVALID_ARG otherwise) and also adds m2 and K; hrt_accum_download works,
+ * but the noise plane and K do not travel, so hrt_accum_upload into one is HRT_ERR_UNSUPPORTED.  Checkpointing the
+ * noise plane, and accumulators whose tiles hold different passes, is out of scope.  hrt_accum_reset also clears
+ * m2, K and the per-tile ranges.  Frame identity, streams and the watchdog's invalid state apply unchanged. */
+/* Render samples [p->sample_offset, + p->samples) of tiles[idx[0..n)] of the accumulator only (indices into the
+ * tile list it was created with) and add them: one megakernel launch and one accumulate kernel, whatever n.
+ * HRT_ERR_INVALID_ARG, with nothing changed: n == 0, an index out of range or given twice, a range that overlaps
+ * the ranges of ANY selected tile. */
+hrt_status hrt_accum_add_tiles(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, const uint32_t* idx, uint32_t n,
+                               void* stream, hrt_render_stats* stats);
+/* One tile's record of hrt_accum_noise (a struct the CALLER allocates an array of; 24 bytes). */
+typedef struct hrt_tile_noise hrt_tile_noise;
+struct hrt_tile_noise {
+  float mean, max;  /* of the tile's per-pixel err */
+  uint64_t samples; /* N of the tile */
+  uint64_t chunks;  /* K of the tile */
+};
+/* The error of every pixel to d_err (device memory, n_pixels floats packed as the tiles are; may be NULL) and one
+ * record per tile to tiles_out (host memory, n_tiles records); synchronises `stream`.  floor <= 0 or NaN is
+ * HRT_ERR_INVALID_ARG; an accumulator without HRT_ACCUM_NOISE, or without samples, HRT_ERR_STATE.  A tile without
+ * samples (or with one chunk) reports +inf. */
+hrt_status hrt_accum_noise(hrt_accum* a, float floor, float* d_err, void* stream, hrt_tile_noise* tiles_out);
+/* The samples each tile holds (n_tiles values). */
+hrt_status hrt_accum_tile_samples(const hrt_accum* a, uint64_t* per_tile);
 
 /* ---- diagnostics ---- */
 /* Device occupancy / layout facts of the committed scene (for DESIGN/bench). */
@@ -471,6 +532,17 @@ hrt_status hrt_debug_box_test(int32_t form, int32_t on_device, const float* boxe
  * that check the arithmetic without a GPU and hold the device to the host bit for bit. */
 hrt_status hrt_debug_accumulate(int32_t on_device, const float* partial, uint32_t n_chunks, uint32_t n, float* acc_inout,
                                 uint64_t samples, int32_t format, void* out);
+/* The noise estimate's arithmetic (csrc/accum.h) for ONE tile of n pixels, on the DEVICE through the real kernels
+ * (accumulate_chunks with moments, accum_noise; on_device = 1: the calling thread's current HIP device) or with the
+ * same code compiled for the host (0): partial is one pass's chunk sums [n_chunks][n] x 4 f32 and sizes its chunks'
+ * sample counts; acc_inout (n x 4 f32) and m2_inout (n f32) are the sums and moments before and after the pass;
+ * samples = N and chunks = K held after it; err_out takes the n errors and mean_max_out the tile's mean and max. */
+hrt_status hrt_debug_noise(int32_t on_device, const float* partial, const uint32_t* sizes, uint32_t n_chunks, uint32_t n,
+                           float* acc_inout, float* m2_inout, uint64_t samples, uint64_t chunks, float floor, float* err_out,
+                           float* mean_max_out);
+/* The noise plane of a HRT_ACCUM_NOISE accumulator (n_pixels f32, packed as the tiles are) into host memory, after a
+ * device synchronisation: for the tests that hold m2 to its bit contract. */
+hrt_status hrt_debug_accum_moments(hrt_accum* a, float* m2_out);
 /* One builder of the sphere walk stream's hierarchy on n bare leaf boxes (n x 6 floats: min
  * xyz, max xyz), the code commit runs: builder 0 the host's greedy split, 1 the host's DP over 2 x half area, 2 the
  * host's DP over half area x leaves, 3 the greedy split with the DP (1) on ranges of at most dp_sub leaves, 4 the
