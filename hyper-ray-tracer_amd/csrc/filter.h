@@ -1,0 +1,159 @@
+/*
+ * filter.h — the arithmetic of the variance-guided a-trous filter (hrt_accum_resolve_filtered, include/hrt/hrt.h),
+ * the same code on the device (filter.hip filter_gather / filter_atrous) and on the host (hrt_debug_filter with
+ * on_device = 0), like accum.h: built with -ffp-contract=off, f32 '/' and sqrtf IEEE correctly rounded on both
+ * sides, so the two give the same bits.
+ *
+ * The bits of a filtered frame are defined by these functions alone.
+ *   Domain: the pixels the accumulator's tiles cover.  A neighbour off the image or covered by no tile is ABSENT and
+ *   contributes to no sum.  On a raster plane a pixel is (c.x, c.y, c.z, v) and an absent one has v < 0.
+ *   Inputs of pixel p, with inv_n and inv_k1 of p's tile (gather):
+ *     c_p = (acc.x * inv_n, acc.y * inv_n, acc.z * inv_n), the linear radiance;
+ *     v_p = accum::variance(m2_p, accum::luma(acc_p), inv_n, inv_k1) * inv_n, the variance of the mean;
+ *     l_p = accum::luma(c_p), recomputed from c wherever it is used.
+ *   Iteration i = 0 .. iterations - 1 with step s = 1 << i reads the planes (c, v) of the previous one, never in
+ *   place (atrous_pixel):
+ *     1. num = den = 0; for dy = -1..1 (outer), dx = -1..1 (inner) over present q = p + (dx, dy):
+ *        g = G[dy + 1] * G[dx + 1], G = {1, 2, 1}; num = num + g * v_q, then den = den + g; vb = num / den.
+ *     2. r = 1 / (sigma * sqrtf(vb) + 1e-6f).
+ *     3. sc = (0, 0, 0), sv = sw = 0; for dy = -2..2 (outer), dx = -2..2 (inner) over present q = p + s * (dx, dy),
+ *        the centre at its place in the order: d = fabsf(l_q - l_p) * r; t = at_least(1 - d * 0.5f, 0); e = t * t,
+ *        e = e * e; w = (H[dy + 2] * H[dx + 2]) * e, H = {1/16, 1/4, 3/8, 1/4, 1/16};
+ *        sc = sc + w * c_q per channel, sv = sv + (w * w) * v_q, sw = sw + w.
+ *     4. c' = sc / sw per channel, v' = sv / (sw * sw); sw == 0 (only reachable through NaN): c' = c_p, v' = v_p.
+ *   Output: sqrtf(c'.x), sqrtf(c'.y), sqrtf(c'.z), 1 (resolve), or accum::resolve_rgba8 of that.
+ * The weight is a polynomial, (1 - d/2)^4 clamped at 0, because it has one form on host and device; an expf has not.
+ */
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "accum.h"
+
+namespace hrt {
+namespace filter {
+
+constexpr uint32_t MAX_ITERATIONS = 5;
+
+/* one pixel of a raster plane; v < 0: absent */
+struct Px {
+  Vec3 c;
+  float v;
+};
+HRT_HD Px px(float x, float y, float z, float v) {
+  Px p;
+  p.c = v3(x, y, z);
+  p.v = v;
+  return p;
+}
+HRT_HD Px absent() { return px(0.0f, 0.0f, 0.0f, -1.0f); }
+HRT_HD bool present(const Px& p) { return !(p.v < 0.0f); }
+
+/* the plane's pixel from the accumulator's sums and moment */
+HRT_HD Px gather(Vec3 acc, float m2, float inv_n, float inv_k1) {
+  Px p;
+  p.c = v3(acc.x * inv_n, acc.y * inv_n, acc.z * inv_n);
+  p.v = accum::variance(m2, accum::luma(acc), inv_n, inv_k1) * inv_n;
+  return p;
+}
+
+HRT_HD float g_tap(int k) { return k == 1 ? 2.0f : 1.0f; }
+HRT_HD float h_tap(int k) { return k == 2 ? 0.375f : ((k == 1 || k == 3) ? 0.25f : 0.0625f); }
+
+/* One iteration at the PRESENT pixel (x, y) with step s.  at(x, y) gives the previous planes' pixel, absent() for a
+ * pixel off the image. */
+template <class At>
+HRT_HD Px atrous_pixel(At at, int x, int y, int s, float sigma) {
+  const Px p = at(x, y);
+  const float lp = accum::luma(p.c);
+  float num = 0.0f, den = 0.0f;
+  for (int dy = -1; dy <= 1; dy++)
+    for (int dx = -1; dx <= 1; dx++) {
+      const Px q = at(x + dx, y + dy);
+      if (!present(q)) continue;
+      const float g = g_tap(dy + 1) * g_tap(dx + 1);
+      num = num + g * q.v;
+      den = den + g;
+    }
+  const float vb = num / den;
+  const float r = 1.0f / (sigma * sqrtf(vb) + 1e-6f);
+  Vec3 sc = v3(0.0f, 0.0f, 0.0f);
+  float sv = 0.0f, sw = 0.0f;
+  for (int dy = -2; dy <= 2; dy++)
+    for (int dx = -2; dx <= 2; dx++) {
+      const Px q = at(x + s * dx, y + s * dy);
+      if (!present(q)) continue;
+      const float d = fabsf(accum::luma(q.c) - lp) * r;
+      const float t = accum::at_least(1.0f - d * 0.5f, 0.0f);
+      float e = t * t;
+      e = e * e;
+      const float w = (h_tap(dy + 2) * h_tap(dx + 2)) * e;
+      sc = sc + w * q.c;
+      sv = sv + (w * w) * q.v;
+      sw = sw + w;
+    }
+  if (sw == 0.0f) return p;
+  Px o;
+  o.c = sc / sw;
+  o.v = sv / (sw * sw);
+  return o;
+}
+
+/* the displayable pixel of a filtered one (alpha is 1) */
+HRT_HD Vec3 resolve(const Px& p) { return v3(sqrtf(p.c.x), sqrtf(p.c.y), sqrtf(p.c.z)); }
+
+/* The host's restatement of a whole raster: in and out are width x height x 4 f32 (c.xyz, v); absent pixels pass
+ * through as they are. */
+inline void filter_raster(const float* in, uint32_t width, uint32_t height, uint32_t iterations, float sigma, float* out) {
+  const size_t n = (size_t)width * height;
+  std::vector<float> a(in, in + 4 * n), b(4 * n);
+  for (uint32_t i = 0; i < iterations; i++) {
+    const float* src = a.data();
+    auto at = [=](int x, int y) {
+      if (x < 0 || y < 0 || x >= (int)width || y >= (int)height) return absent();
+      const float* q = src + 4 * ((size_t)y * width + (size_t)x);
+      return px(q[0], q[1], q[2], q[3]);
+    };
+    for (uint32_t y = 0; y < height; y++)
+      for (uint32_t x = 0; x < width; x++) {
+        const Px p = at((int)x, (int)y);
+        const Px o = present(p) ? atrous_pixel(at, (int)x, (int)y, 1 << i, sigma) : p;
+        float* d = b.data() + 4 * ((size_t)y * width + x);
+        d[0] = o.c.x, d[1] = o.c.y, d[2] = o.c.z, d[3] = o.v;
+      }
+    a.swap(b);
+  }
+  for (size_t k = 0; k < 4 * n; k++) out[k] = a[k];
+}
+
+/* ---- the launches of filter.hip, for the accumulator code in render.hip (streams are hipStream_t) ---- */
+
+/* One tile as filter_gather and the last filter_atrous see it.  The tile-block domain: a tile is cut into
+ * BLOCK_W x BLOCK_H pixel blocks, row-major, and the tiles' blocks are numbered in tile order starting at blk0. */
+constexpr uint32_t BLOCK_W = 32, BLOCK_H = 8;
+struct alignas(16) FilterTile {
+  uint32_t x, y, w, h; /* in plane coordinates: the image's minus the bounding box's corner */
+  uint32_t off;        /* first pixel in the packed order */
+  uint32_t blk0;       /* first block of the tile-block domain */
+  float inv_n;         /* accum::resolve_scale(samples) */
+  float inv_k1;        /* accum::chunks_scale(chunks) */
+};
+inline uint32_t tile_blocks(uint32_t w, uint32_t h) { return ((w + BLOCK_W - 1) / BLOCK_W) * ((h + BLOCK_H - 1) / BLOCK_H); }
+
+/* the steps staged in LDS; larger ones read their taps from global memory */
+constexpr uint32_t LDS_MAX_STEP = 4;
+
+/* format of the last iteration's packed output: HRT_ACCUM_F32, HRT_ACCUM_RGBA8, or RAW: float4 (c', v') */
+constexpr int32_t FORMAT_RAW = -1;
+
+/* acc, m2 (packed) -> plane (plane_w x plane_h float4) at the tiles' pixels */
+void launch_gather(const void* d_acc, const float* d_m2, const FilterTile* d_tiles, uint32_t n_tiles, uint32_t n_blocks,
+                   void* d_plane, uint32_t plane_w, void* stream);
+/* `iterations` of the filter from plane a (b is the other plane; both are written), the last one to d_out packed */
+void launch_atrous(void* d_a, void* d_b, uint32_t plane_w, uint32_t plane_h, const FilterTile* d_tiles, uint32_t n_tiles,
+                   uint32_t n_blocks, uint32_t iterations, float sigma, int32_t format, void* d_out, void* stream);
+
+}  // namespace filter
+}  // namespace hrt

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "accum.h"
+#include "filter.h"
 #include "primary_list.h"
 #include "kernel_common.h"
 
@@ -1380,6 +1381,13 @@ struct hrt_accum {
   NoiseTile* d_ntiles = nullptr; /* n_tiles records for accum_noise / accum_resolve_tiles, and their host copy */
   float2* d_nout = nullptr;      /* n_tiles x (mean, max) */
   std::vector<NoiseTile> h_ntiles;
+  /* The filtered resolve's buffers (filter.h), made by the first hrt_accum_resolve_filtered: two raster planes over
+   * the tiles' bounding box and the tiles in plane coordinates.  f_state: 0 not made yet, 1 made, -1 the tiles overlap */
+  int f_state = 0;
+  uint32_t f_w = 0, f_h = 0, f_blocks = 0;
+  float4* d_fplane[2] = {nullptr, nullptr};
+  filter::FilterTile* d_ftiles = nullptr;
+  std::vector<filter::FilterTile> h_ftiles;
   bool uniform() const { return tile_ranges.empty(); }
   const std::vector<SampleRange>& ranges_of(size_t t) const { return uniform() ? ranges : tile_ranges[t]; }
   uint64_t chunks_of(size_t t) const { return uniform() ? chunks : tile_chunks[t]; }
@@ -1454,6 +1462,89 @@ void launch_resolve(hrt_accum* a, int32_t format, void* d_out, hipStream_t strea
     hipLaunchKernelGGL((accum_resolve<HRT_ACCUM_RGBA8>), dim3(stream_blocks(a->n_px)), dim3(256), 0, stream, (const float4*)a->d_acc,
                        a->n_px, scale, d_out);
   hip_check(hipGetLastError(), "accum_resolve launch");
+}
+
+/* hrt_accum_resolve_filtered's checks: nothing changes on an error */
+void filter_args(const hrt_filter_params* f) {
+  if (f->iterations < 1 || f->iterations > filter::MAX_ITERATIONS)
+    throw HipError{HRT_ERR_INVALID_ARG, "hrt_filter_params: iterations outside [1, 5]"};
+  if (!(f->sigma > 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_filter_params: sigma must be > 0"};
+}
+void filter_state(const hrt_accum* a) {
+  accum_usable(a);
+  if (!a->d_m2) throw HipError{HRT_ERR_STATE, "hrt_accum_resolve_filtered: the accumulator was created without HRT_ACCUM_NOISE"};
+  if (accum_empty(a)) throw HipError{HRT_ERR_STATE, "the accumulator holds no samples"};
+  for (size_t t = 0; t < a->tiles.size(); t++)
+    if (a->ranges_of(t).empty() || a->chunks_of(t) < 2)
+      throw HipError{HRT_ERR_STATE, "hrt_accum_resolve_filtered: a tile holds no samples or fewer than 2 chunks (no variance estimate)"};
+}
+/* the planes and the tile records, once per accumulator: its tiles never change */
+void filter_prepare(hrt_accum* a, hipStream_t stream) {
+  if (a->f_state < 0) throw HipError{HRT_ERR_UNSUPPORTED, "hrt_accum_resolve_filtered: the accumulator's tiles overlap"};
+  if (a->f_state > 0) return;
+  uint32_t x0 = UINT32_MAX, y0 = UINT32_MAX, x1 = 0, y1 = 0;
+  for (const hrt_tile& t : a->tiles) {
+    x0 = std::min(x0, t.x), y0 = std::min(y0, t.y);
+    x1 = std::max(x1, t.x + t.w), y1 = std::max(y1, t.y + t.h);
+  }
+  const uint32_t w = x1 - x0, h = y1 - y0;
+  const size_t area = (size_t)w * h;
+  /* disjoint tiles cover as many pixels as they hold */
+  std::vector<bool> covered(area, false);
+  for (const hrt_tile& t : a->tiles)
+    for (uint32_t y = t.y - y0; y < t.y - y0 + t.h; y++)
+      for (uint32_t x = t.x - x0; x < t.x - x0 + t.w; x++) {
+        if (covered[(size_t)y * w + x]) {
+          a->f_state = -1;
+          throw HipError{HRT_ERR_UNSUPPORTED, "hrt_accum_resolve_filtered: the accumulator's tiles overlap"};
+        }
+        covered[(size_t)y * w + x] = true;
+      }
+  std::vector<filter::FilterTile> ft(a->tiles.size());
+  uint64_t blocks = 0;
+  for (size_t t = 0; t < ft.size(); t++) {
+    const hrt_tile& T = a->tiles[t];
+    ft[t] = filter::FilterTile{T.x - x0, T.y - y0, T.w, T.h, a->tile_off[t], (uint32_t)blocks, 0.0f, 0.0f};
+    blocks += filter::tile_blocks(T.w, T.h);
+  }
+  if (blocks >= (1ull << 31)) throw HipError{HRT_ERR_UNSUPPORTED, "hrt_accum_resolve_filtered: too many tile blocks for one launch"};
+  float4* plane[2] = {nullptr, nullptr};
+  filter::FilterTile* d_ft = nullptr;
+  try {
+    for (float4*& pl : plane) hip_check(hipMalloc((void**)&pl, area * sizeof(float4)), "hipMalloc(filter plane)");
+    hip_check(hipMalloc((void**)&d_ft, ft.size() * sizeof(filter::FilterTile)), "hipMalloc(filter tiles)");
+    /* pixels no tile covers are absent: v < 0 (0xBFBFBFBF is -1.498).  filter_gather writes the covered ones of
+     * plane 0 alone and every iteration passes absent pixels on, so once is enough; it is waited for, so that a
+     * later resolve on another stream finds it done */
+    if (a->n_px != area) {
+      hip_check(hipMemsetAsync(plane[0], 0xBF, area * sizeof(float4), stream), "hipMemsetAsync(filter plane)");
+      hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize(filter plane)");
+    }
+  } catch (...) {
+    for (float4* pl : plane)
+      if (pl) (void)hipFree(pl);
+    if (d_ft) (void)hipFree(d_ft);
+    throw;
+  }
+  a->d_fplane[0] = plane[0], a->d_fplane[1] = plane[1];
+  a->d_ftiles = d_ft;
+  a->h_ftiles.swap(ft);
+  a->f_w = w, a->f_h = h, a->f_blocks = (uint32_t)blocks;
+  a->f_state = 1;
+}
+void launch_filtered(hrt_accum* a, const hrt_filter_params* f, int32_t format, void* d_out, hipStream_t stream) {
+  filter_prepare(a, stream);
+  upload_noise_tiles(a, stream); /* each tile's own 1 / N and 1 / (K - 1) */
+  const uint32_t nt = (uint32_t)a->tiles.size();
+  for (uint32_t t = 0; t < nt; t++) {
+    a->h_ftiles[t].inv_n = a->h_ntiles[t].inv_n;
+    a->h_ftiles[t].inv_k1 = a->h_ntiles[t].inv_k1;
+  }
+  hip_check(hipMemcpyAsync(a->d_ftiles, a->h_ftiles.data(), nt * sizeof(filter::FilterTile), hipMemcpyHostToDevice, stream),
+            "hipMemcpyAsync(filter tiles)");
+  filter::launch_gather(a->d_acc, a->d_m2, a->d_ftiles, nt, a->f_blocks, a->d_fplane[0], a->f_w, stream);
+  filter::launch_atrous(a->d_fplane[0], a->d_fplane[1], a->f_w, a->f_h, a->d_ftiles, nt, a->f_blocks, f->iterations, f->sigma,
+                        format, d_out, stream);
 }
 
 /* K of a pass: the chunks its schedule sums a pixel's samples in */
@@ -1861,6 +1952,9 @@ void hrt_accum_destroy(hrt_accum* a) {
   if (a->d_m2) (void)hipFree(a->d_m2);
   if (a->d_ntiles) (void)hipFree(a->d_ntiles);
   if (a->d_nout) (void)hipFree(a->d_nout);
+  for (float4* plane : a->d_fplane)
+    if (plane) (void)hipFree(plane);
+  if (a->d_ftiles) (void)hipFree(a->d_ftiles);
   if (prev >= 0) (void)hipSetDevice(prev);
   delete a;
 }
@@ -1980,6 +2074,35 @@ hrt_status hrt_accum_resolve_host(hrt_accum* a, int32_t format, void* out) {
     hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize"); /* passes the caller queued on any stream */
     launch_resolve(a, format, buf.ptr, nullptr);
     hip_check(hipMemcpy(out, buf.ptr, bytes, hipMemcpyDeviceToHost), "hipMemcpy(resolve)");
+  });
+  if (a && buf.ptr) out_pool_give(a->scene, buf);
+  return st;
+}
+
+hrt_status hrt_accum_resolve_filtered(hrt_accum* a, const hrt_filter_params* f, int32_t format, void* d_out, void* stream) {
+  return hguard([&] {
+    if (!a || !f || !d_out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_resolve_filtered: null argument"};
+    accum_format(format);
+    filter_args(f);
+    filter_state(a);
+    DeviceGuard dg(a->device);
+    launch_filtered(a, f, format, d_out, (hipStream_t)stream);
+  });
+}
+
+hrt_status hrt_accum_resolve_filtered_host(hrt_accum* a, const hrt_filter_params* f, int32_t format, void* out) {
+  OutBuf buf{nullptr, 0};
+  const hrt_status st = hguard([&] {
+    if (!a || !f || !out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_resolve_filtered_host: null argument"};
+    accum_format(format);
+    filter_args(f);
+    filter_state(a);
+    DeviceGuard dg(a->device);
+    const size_t bytes = a->n_px * (format == HRT_ACCUM_F32 ? 16u : 4u);
+    buf = out_pool_take(a->scene, a->n_px * 16 + 16);
+    hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize"); /* passes the caller queued on any stream */
+    launch_filtered(a, f, format, buf.ptr, nullptr);
+    hip_check(hipMemcpy(out, buf.ptr, bytes, hipMemcpyDeviceToHost), "hipMemcpy(filtered resolve)");
   });
   if (a && buf.ptr) out_pool_give(a->scene, buf);
   return st;
@@ -2162,6 +2285,28 @@ hrt_status hrt_debug_noise(int32_t on_device, const float* partial, const uint32
     hip_check(hipMemcpy(m2_inout, d_m2.p, m_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
     hip_check(hipMemcpy(err_out, d_err.p, m_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
     hip_check(hipMemcpy(mean_max_out, d_rec.p, sizeof(float2), hipMemcpyDeviceToHost), "hipMemcpy");
+  });
+}
+
+hrt_status hrt_debug_filter(int32_t on_device, const float* raster, uint32_t width, uint32_t height, uint32_t iterations,
+                            float sigma, float* out) {
+  return hguard([&] {
+    if (!raster || !out || width == 0 || height == 0 || width > 65535 || height > 65535)
+      throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_filter: null argument, or a width or height outside [1, 65535]"};
+    const hrt_filter_params f{iterations, sigma};
+    filter_args(&f);
+    if (!on_device) return filter::filter_raster(raster, width, height, iterations, sigma, out);
+    /* the real kernels on the calling thread's current device: one tile that covers the raster, so the packed
+     * order of the last iteration's output is the raster's */
+    const size_t bytes = (size_t)width * height * sizeof(float4);
+    DevBuf<float4> d_a(bytes), d_b(bytes), d_out(bytes);
+    DevBuf<filter::FilterTile> d_tile(sizeof(filter::FilterTile));
+    const filter::FilterTile T{0, 0, width, height, 0, 0, 0.0f, 0.0f};
+    hip_check(hipMemcpy(d_a.p, raster, bytes, hipMemcpyHostToDevice), "hipMemcpy");
+    hip_check(hipMemcpy(d_tile.p, &T, sizeof(T), hipMemcpyHostToDevice), "hipMemcpy");
+    filter::launch_atrous(d_a.p, d_b.p, width, height, d_tile.p, 1, filter::tile_blocks(width, height), iterations, sigma,
+                          filter::FORMAT_RAW, d_out.p, nullptr);
+    hip_check(hipMemcpy(out, d_out.p, bytes, hipMemcpyDeviceToHost), "hipMemcpy");
   });
 }
 

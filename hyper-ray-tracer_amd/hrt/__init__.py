@@ -148,6 +148,11 @@ class TileNoise(ctypes.Structure):
     _fields_ = [("mean", ctypes.c_float), ("max", ctypes.c_float), ("samples", ctypes.c_uint64), ("chunks", ctypes.c_uint64)]
 
 
+class FilterParams(ctypes.Structure):
+    """hrt_filter_params: the a-trous filter's iterations (1..5) and luminance tolerance in standard errors."""
+    _fields_ = [("iterations", ctypes.c_uint32), ("sigma", ctypes.c_float)]
+
+
 class SceneOptions(ctypes.Structure):
     """hrt_scene_options: the explicit configuration that can change an image's bits (all-zero = default)."""
     _fields_ = [(n, ctypes.c_uint32) for n in ("bvh_ties", "walk_tree", "chunk_min", "chunk_max", "chunk_uniform")]
@@ -160,7 +165,8 @@ OPTIONAL = {"hrt_abi_version", "hrt_last_launch", "hrt_debug_box_test", "hrt_sce
             "hrt_accum_samples", "hrt_accum_resolve", "hrt_accum_resolve_host", "hrt_accum_merge", "hrt_accum_download",
             "hrt_accum_upload", "hrt_debug_accumulate", "hrt_debug_walk_regroup",
             "hrt_accum_create_ex", "hrt_accum_add_tiles", "hrt_accum_noise", "hrt_accum_tile_samples", "hrt_debug_noise",
-            "hrt_debug_accum_moments"}
+            "hrt_debug_accum_moments",
+            "hrt_accum_resolve_filtered", "hrt_accum_resolve_filtered_host", "hrt_debug_filter"}
 HRT_LIB_OVERRIDE = bool(os.environ.get("HRT_LIB"))
 
 # Every entry point of include/hrt/hrt.h (tests/test_abi.py checks the header against this list).
@@ -180,6 +186,7 @@ EXPORTS = [
     "hrt_debug_accumulate", "hrt_debug_walk_regroup",
     "hrt_accum_create_ex", "hrt_accum_add_tiles", "hrt_accum_noise", "hrt_accum_tile_samples", "hrt_debug_noise",
     "hrt_debug_accum_moments",
+    "hrt_accum_resolve_filtered", "hrt_accum_resolve_filtered_host", "hrt_debug_filter",
 ]
 
 ABI_VERSION = 6  # include/hrt/hrt.h HRT_ABI_VERSION: the struct layouts below
@@ -279,6 +286,9 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "hrt_accum_tile_samples": (S, [vp, vp]),
         "hrt_debug_noise": (S, [i32, vp, vp, u32, u32, vp, vp, u64, u64, f, vp, vp]),
         "hrt_debug_accum_moments": (S, [vp, vp]),
+        "hrt_accum_resolve_filtered": (S, [vp, ctypes.POINTER(FilterParams), i32, vp, vp]),
+        "hrt_accum_resolve_filtered_host": (S, [vp, ctypes.POINTER(FilterParams), i32, vp]),
+        "hrt_debug_filter": (S, [i32, vp, u32, u32, u32, f, vp]),
     }
     for name, (res, args) in sig.items():
         if name in OPTIONAL and HRT_LIB_OVERRIDE and not hasattr(L, name):
@@ -556,6 +566,11 @@ ACCUM_NOISE = 1  # hrt_accum_create_ex flag
 _ACCUM_FORMATS = {"f32": ACCUM_F32, "rgba8": ACCUM_RGBA8}
 
 
+def filter_params(iterations: int = 3, sigma: float = 4.0) -> FilterParams:
+    """hrt_filter_params with the defaults of Accumulator.resolve(denoise=True)."""
+    return FilterParams(int(iterations), float(sigma))
+
+
 class Accumulator:
     """hrt_accum: device-resident raw per-pixel sums of a tile set (the whole frame when `tiles` is None).  Passes
     add sample ranges (`add` with params.sample_offset / params.samples), and `resolve` gives the frame of the
@@ -687,11 +702,17 @@ class Accumulator:
             if not todo:
                 return rec
 
-    def resolve(self, fmt: str = "f32") -> np.ndarray:
+    def resolve(self, fmt: str = "f32", denoise=None) -> np.ndarray:
         """The frame of the samples held: float32 sqrt(sum / samples) with alpha 1 shaped like hrt.render's result,
-        or uint8 (the PPM rule, alpha 255); several tiles: packed (n_pixels, 4)."""
+        or uint8 (the PPM rule, alpha 255); several tiles: packed (n_pixels, 4).  denoise (a noise=True accumulator):
+        the frame through the variance-guided a-trous filter instead (hrt_accum_resolve_filtered_host); True means
+        dict(iterations=3, sigma=4.0), a dict overrides either value.  A preview for noisy scenes, never a default."""
         out = np.zeros(self.n_pixels * 4, np.float32 if fmt == "f32" else np.uint8)
-        _check(load().hrt_accum_resolve_host(self.h, _ACCUM_FORMATS[fmt], out.ctypes.data))
+        if denoise is None or denoise is False:
+            _check(load().hrt_accum_resolve_host(self.h, _ACCUM_FORMATS[fmt], out.ctypes.data))
+            return self._shaped(out)
+        f = filter_params(**({} if denoise is True else dict(denoise)))
+        _check(load().hrt_accum_resolve_filtered_host(self.h, ctypes.byref(f), _ACCUM_FORMATS[fmt], out.ctypes.data))
         return self._shaped(out)
 
     def merge(self, other: "Accumulator"):
@@ -750,6 +771,19 @@ def debug_noise(partial: np.ndarray, sizes, acc: np.ndarray, m2: np.ndarray, sam
     _check(load().hrt_debug_noise(1 if on_device else 0, pa.ctypes.data, sz.ctypes.data, n_chunks, n, a.ctypes.data, m.ctypes.data,
                                   int(samples), int(chunks), float(floor), err.ctypes.data, mm.ctypes.data))
     return a, m, err, mm[0], mm[1]
+
+
+def debug_filter(raster: np.ndarray, iterations: int, sigma: float, on_device: bool = False) -> np.ndarray:
+    """hrt_debug_filter: the a-trous filter's iterations (csrc/filter.h) on the host, or through the real kernel on
+    the current device.  raster: (height, width, 4) float32 (c.xyz, v; v < 0: an absent pixel).  Returns the same
+    shape: (c'.xyz before the sqrt, v'); absent pixels come out as they went in."""
+    r = np.ascontiguousarray(raster, np.float32)
+    if r.ndim != 3 or r.shape[2] != 4:
+        raise ValueError("raster must be (height, width, 4) float32")
+    out = np.zeros_like(r)
+    _check(load().hrt_debug_filter(1 if on_device else 0, r.ctypes.data, r.shape[1], r.shape[0], int(iterations), float(sigma),
+                                   out.ctypes.data))
+    return out
 
 
 WALK_GREEDY, WALK_DP_AREA, WALK_DP_LEAVES, WALK_GREEDY_SUB, WALK_DEVICE = range(5)

@@ -426,6 +426,50 @@ hrt_status hrt_accum_noise(hrt_accum* a, float floor, float* d_err, void* stream
 /* The samples each tile holds (n_tiles values). */
 hrt_status hrt_accum_tile_samples(const hrt_accum* a, uint64_t* per_tile);
 
+/* ---- variance-guided preview filter ----
+ * An opt-in resolve of a HRT_ACCUM_NOISE accumulator for previews of noisy scenes: an edge-stopping a-trous filter
+ * whose tolerance at each pixel comes from the noise plane.  It uses no feature buffers (albedo, normal, depth), so it
+ * blurs detail that is smaller than its footprint and no noisier than its surroundings: it is never a default
+ * (README.md, DESIGN.md section 6.7 say where it helps and where it hurts).
+ *
+ * THE BIT CONTRACT of the filtered frame (csrc/filter.h, -ffp-contract=off, IEEE '/' and sqrtf, all in f32):
+ *   Domain: the pixels the accumulator's tiles cover.  A neighbour that is off the image, or covered by no tile, is
+ *   ABSENT and contributes to no sum.  An accumulator whose tiles overlap is HRT_ERR_UNSUPPORTED.
+ *   Inputs of pixel p, with inv_n = 1.0f / (float)N and inv_k1 = 1.0f / (float)(K - 1) of p's tile:
+ *     c_p = (acc.x * inv_n, acc.y * inv_n, acc.z * inv_n), the linear radiance; l_p = (c_p.x + c_p.y) + c_p.z;
+ *     v_p = var * inv_n with var of the noise contract above (Y = luma(acc_p)): the variance of the mean.
+ *   Iterations i = 0 .. iterations - 1 with step s = 1 << i; each reads the planes (c, v) of the previous one and is
+ *   never in place:
+ *     1. Prefiltered variance: num = den = 0.0f; for dy = -1..1 (outer), dx = -1..1 (inner) over present
+ *        q = p + (dx, dy): g = G[dy + 1] * G[dx + 1] with G = {1, 2, 1}; num = num + g * v_q, then den = den + g;
+ *        vb = num / den.
+ *     2. Scale: r = 1.0f / (sigma * sqrtf(vb) + 1e-6f).
+ *     3. Taps: sc = (0, 0, 0), sv = 0, sw = 0; for dy = -2..2 (outer), dx = -2..2 (inner) over present
+ *        q = p + s * (dx, dy), the centre included at its place in the order: d = fabsf(l_q - l_p) * r;
+ *        t = (1.0f - d * 0.5f) if that is > 0, else 0; e = t * t, then e = e * e; w = (H[dy + 2] * H[dx + 2]) * e with
+ *        H = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f}; sc = sc + w * c_q per channel, sv = sv + (w * w) * v_q,
+ *        sw = sw + w.
+ *     4. Result: c' = sc / sw per channel, v' = sv / (sw * sw); if sw == 0 (only reachable through NaN), c' = c_p and
+ *        v' = v_p.
+ *   Output: sqrtf(c'.x), sqrtf(c'.y), sqrtf(c'.z), 1 as HRT_ACCUM_F32, or the PPM rule on that as HRT_ACCUM_RGBA8,
+ *   packed as the tiles are.
+ * So the filtered frame is a function of the sums, the planes and the covered pixel set: it does not depend on how
+ * that set is cut into tiles.  A filtered resolve never writes the sums or m2: resolve, noise and later passes give
+ * the bits they would have given.  Tiles that hold different passes are supported (each with its own N and K).
+ * Two raster planes of 16 B per pixel of the tiles' bounding box are allocated by the first filtered resolve and
+ * freed with the accumulator; the work is stream-ordered on `stream`.
+ * Errors, each changing nothing: HRT_ERR_INVALID_ARG for iterations outside [1, 5], sigma <= 0 or NaN, an unknown
+ * format, null pointers; HRT_ERR_STATE for an accumulator without HRT_ACCUM_NOISE, without samples, with a tile that
+ * holds no samples or fewer than 2 chunks, or in the watchdog's invalid state. */
+typedef struct hrt_filter_params hrt_filter_params;
+struct hrt_filter_params { /* 8 bytes */
+  uint32_t iterations; /* 1 .. 5: footprint radius 2 * (2^iterations - 1) px */
+  float sigma;         /* > 0: luminance tolerance in standard errors; 4 is a good start */
+};
+hrt_status hrt_accum_resolve_filtered(hrt_accum* a, const hrt_filter_params* f, int32_t format, void* d_out, void* stream);
+/* ... into HOST memory; waits for the device as hrt_accum_resolve_host does */
+hrt_status hrt_accum_resolve_filtered_host(hrt_accum* a, const hrt_filter_params* f, int32_t format, void* out);
+
 /* ---- diagnostics ---- */
 /* Device occupancy / layout facts of the committed scene (for DESIGN/bench). */
 typedef struct hrt_scene_info {
@@ -543,6 +587,12 @@ hrt_status hrt_debug_noise(int32_t on_device, const float* partial, const uint32
 /* The noise plane of a HRT_ACCUM_NOISE accumulator (n_pixels f32, packed as the tiles are) into host memory, after a
  * device synchronisation: for the tests that hold m2 to its bit contract. */
 hrt_status hrt_debug_accum_moments(hrt_accum* a, float* m2_out);
+/* The filter's iterations (csrc/filter.h) on a raster the caller gives, on the DEVICE through filter_atrous
+ * (on_device = 1: the calling thread's current HIP device) or with the same arithmetic on the host (0).
+ * raster: width x height x 4 f32 (c.xyz, v; v < 0: absent); out: width x height x 4 f32 (c'.xyz BEFORE the sqrt, v');
+ * an absent pixel comes out as it went in.  1 <= width, height <= 65535. */
+hrt_status hrt_debug_filter(int32_t on_device, const float* raster, uint32_t width, uint32_t height, uint32_t iterations,
+                            float sigma, float* out);
 /* One builder of the sphere walk stream's hierarchy on n bare leaf boxes (n x 6 floats: min
  * xyz, max xyz), the code commit runs: builder 0 the host's greedy split, 1 the host's DP over 2 x half area, 2 the
  * host's DP over half area x leaves, 3 the greedy split with the DP (1) on ranges of at most dp_sub leaves, 4 the

@@ -1,0 +1,317 @@
+"""The variance-guided a-trous filter on the GPU (filter.hip through hrt.debug_filter(on_device=True) and
+hrt.Accumulator.resolve(denoise=...)): the bit contract of include/hrt/hrt.h.
+
+The device's iterations equal the host's; an accumulator's filtered frame equals the numpy restatement
+(tests/filter_restated.py) fed from its sums, its noise plane and its tile records; the frame does not depend on the
+tile split; tiles that hold different passes and accumulators over a subset of the image work; the filter changes
+nothing in the accumulator; it brings a noisy Cornell preview closer to the converged frame; and errors change nothing.
+
+Input A = `random` (scene seed 1, render seed 7) at 64x36 in 16-px tiles (tests/test_gpu_accum_noise.py)."""
+import numpy as np
+import pytest
+
+import filter_restated as R
+import hrt
+from oracle import oracle as O
+
+SEED = 7
+FLOOR = 0.05
+F = np.float32
+W, H = 64, 36
+PASSES = [(0, 40), (40, 110), (110, 126)]
+DENOISE = dict(iterations=3, sigma=4)
+
+
+def u32(a):
+    return np.ascontiguousarray(a, F).view(np.uint32)
+
+
+_scenes = {}
+
+
+@pytest.fixture(scope="module")
+def scene(earth):
+    def get(name):
+        if name not in _scenes:
+            s = hrt.preset(name, 1, earth)
+            s.commit()
+            _scenes[name] = s
+        return _scenes[name]
+
+    yield get
+    for s in _scenes.values():
+        s.close()
+    _scenes.clear()
+
+
+def setup(s, w, h, spp, offset=0, seed=SEED):
+    cam = hrt.preset_camera(s.info, w, h)
+    return cam, hrt.params(w, h, spp, 50, seed, tuple(s.info.background), sample_offset=offset)
+
+
+def accumulator(s, w, h, ranges, noise=True, tiles="grid"):
+    a = hrt.Accumulator(s, w, h, hrt.tile_grid(w, h, 16) if tiles == "grid" else tiles, noise=noise)
+    for b, e in ranges:
+        a.add(*setup(s, w, h, e - b, offset=b))
+    return a
+
+
+def scales_of(a):
+    return [R.tile_scales(r.samples, r.chunks) for r in a.noise(FLOOR)]
+
+
+def unpack(a, px, w, h):
+    frame = np.zeros((h, w, 4), px.dtype)
+    off = 0
+    for x, y, tw, th in a.tiles:
+        frame[y:y + th, x:x + tw] = px[off:off + tw * th].reshape(th, tw, 4)
+        off += tw * th
+    return frame
+
+
+# ------------------------------------------------------------------------------------------ 1. device against host
+def raster(w, h, absent):
+    rng = np.random.default_rng(100 * w + h)
+    r = np.zeros((h, w, 4), F)
+    r[..., :3] = rng.uniform(0.0, 2.0, (h, w, 3)).astype(F)
+    r[..., 3] = (10.0 ** rng.uniform(-8.0, 0.0, (h, w))).astype(F)
+    if absent:
+        gone = rng.uniform(size=(h, w)) < 0.08
+        gone[:, w // 2] = True
+        gone[h - 1, :5] = True
+        r[gone, :3] = rng.uniform(-5.0, 5.0, (int(gone.sum()), 3)).astype(F)
+        r[gone, 3] = -rng.uniform(0.5, 2.0, int(gone.sum())).astype(F)
+    return r
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("h", [7, 8, 9, 40])
+@pytest.mark.parametrize("w", [31, 32, 33, 70])
+def test_device_filter_equals_host(w, h):
+    """32 x 8 blocks: one short of, exactly, and one past a block in both directions, and 70 x 40 (three by five
+    blocks); 5 iterations end at step 16, whose footprint (radius 32) is wider than every one of these rasters, and
+    pass the LDS steps (1, 2, 4) and the global ones (8, 16), each both as an inner and as the last iteration."""
+    for absent in (False, True):
+        r = raster(w, h, absent)
+        for it in (1, 2, 3, 4, 5):
+            host, dev = hrt.debug_filter(r, it, 4.0), hrt.debug_filter(r, it, 4.0, on_device=True)
+            assert np.array_equal(u32(dev), u32(host)), (w, h, absent, it)
+    r = raster(w, h, True)
+    assert np.array_equal(u32(hrt.debug_filter(r, 3, 0.5, on_device=True)), u32(hrt.debug_filter(r, 3, 0.5)))
+
+
+# ------------------------------------------------------------------------------------------ 2. the accumulator path
+@pytest.mark.gpu
+def test_filtered_resolve_equals_the_restatement_and_changes_nothing(scene):
+    s = scene("random")
+    a = accumulator(s, W, H, PASSES)
+    sums, held = a.download()
+    m2, px = a.moments(), a.resolve()
+    rec, err = a.noise(FLOOR, error_map=True)
+    assert [(r.samples, r.chunks) for r in rec] == [(126, rec[0].chunks)] * 12 and rec[0].chunks >= 3
+    want = R.filtered_frame(sums, m2, a.tiles, scales_of(a), W, H, 3, 4.0)
+    got = a.resolve(denoise=DENOISE)
+    assert got.shape == (W * H, 4) and got.dtype == F
+    assert np.array_equal(u32(got), u32(want))
+    assert (got[:, 3] == 1).all() and not np.array_equal(got, px)
+    assert np.array_equal(u32(a.resolve(denoise=True)), u32(want))          # True: iterations 3, sigma 4
+    got8 = a.resolve("rgba8", denoise=DENOISE)
+    assert got8.dtype == np.uint8 and np.array_equal(got8, R.quantize(got))
+    one = a.resolve(denoise=dict(iterations=1))                               # a dict overrides either value
+    assert np.array_equal(u32(one), u32(R.filtered_frame(sums, m2, a.tiles, scales_of(a), W, H, 1, 4.0)))
+    five = a.resolve(denoise=dict(iterations=5, sigma=0.5))
+    assert np.array_equal(u32(five), u32(R.filtered_frame(sums, m2, a.tiles, scales_of(a), W, H, 5, 0.5)))
+    # the accumulator is as it was
+    again, held2 = a.download()
+    rec2, err2 = a.noise(FLOOR, error_map=True)
+    assert held2 == held and np.array_equal(u32(again), u32(sums)) and np.array_equal(u32(a.moments()), u32(m2))
+    assert np.array_equal(u32(a.resolve()), u32(px)) and np.array_equal(u32(err2), u32(err))
+    assert [(r.mean, r.max, r.samples, r.chunks) for r in rec2] == [(r.mean, r.max, r.samples, r.chunks) for r in rec]
+    # and a later pass gives the bits it would have given
+    a.add(*setup(s, W, H, 40, offset=126))
+    b = accumulator(s, W, H, PASSES + [(126, 166)])
+    assert np.array_equal(u32(a.download()[0]), u32(b.download()[0])) and np.array_equal(u32(a.moments()), u32(b.moments()))
+    assert np.array_equal(u32(a.resolve(denoise=DENOISE)), u32(b.resolve(denoise=DENOISE)))
+    a.close()
+    b.close()
+
+
+@pytest.mark.gpu
+def test_filtered_frame_does_not_depend_on_the_tile_split(scene):
+    s = scene("random")
+    tiled, whole = accumulator(s, W, H, PASSES), accumulator(s, W, H, PASSES, tiles=None)
+    ragged = accumulator(s, W, H, PASSES, tiles=[(0, 0, 37, 36), (37, 0, 27, 9), (37, 9, 27, 27)])
+    ft, fw = tiled.resolve(denoise=DENOISE), whole.resolve(denoise=DENOISE)
+    assert fw.shape == (H, W, 4)
+    assert np.array_equal(u32(unpack(tiled, ft, W, H)), u32(fw))
+    assert np.array_equal(u32(unpack(ragged, ragged.resolve(denoise=DENOISE), W, H)), u32(fw))
+    for fmt in ("f32", "rgba8"):
+        five = dict(iterations=5, sigma=2.0)
+        assert np.array_equal(unpack(tiled, tiled.resolve(fmt, denoise=five), W, H), whole.resolve(fmt, denoise=five))
+    for x in (tiled, whole, ragged):
+        x.close()
+
+
+@pytest.mark.gpu
+def test_tiles_that_hold_different_passes(scene):
+    """After a second pass over tiles 1, 4 and 11 alone each tile filters with its own 1 / N and 1 / (K - 1); a tile's
+    sums and moments are those of a uniform accumulator with that tile's passes (tests/test_gpu_accum_noise.py)."""
+    s = scene("random")
+    subset = [1, 4, 11]
+    first, both = accumulator(s, W, H, [(0, 40)]), accumulator(s, W, H, [(0, 40), (40, 80)])
+    sub = accumulator(s, W, H, [(0, 40)])
+    sub.add(*setup(s, W, H, 40, offset=40), tiles=subset)
+    assert sub.tile_samples == [80 if t in subset else 40 for t in range(12)]
+    sums, m2 = first.download()[0].copy(), first.moments().copy()
+    off = 0
+    for t, (_, _, tw, th) in enumerate(sub.tiles):
+        if t in subset:
+            sums[off:off + tw * th] = both.download()[0][off:off + tw * th]
+            m2[off:off + tw * th] = both.moments()[off:off + tw * th]
+        off += tw * th
+    assert np.array_equal(u32(sub.moments()), u32(m2))
+    scales = scales_of(sub)
+    assert len(set(scales)) == 2
+    for it in (1, 3):
+        want = R.filtered_frame(sums, m2, sub.tiles, scales, W, H, it, 4.0)
+        assert np.array_equal(u32(sub.resolve(denoise=dict(iterations=it))), u32(want)), it
+    for x in (first, both, sub):
+        x.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("subset", [[0, 1, 4, 5], [0, 5, 10]])
+def test_subset_accumulator(scene, subset):
+    """An accumulator over some tiles of the grid: pixels outside them are absent, both those off the tiles' bounding
+    box ([0, 1, 4, 5] fills its box) and those inside it that no tile covers ([0, 5, 10] lies on a diagonal)."""
+    s = scene("random")
+    grid = hrt.tile_grid(W, H, 16)
+    a = accumulator(s, W, H, PASSES, tiles=[grid[t] for t in subset])
+    sums, m2 = a.download()[0], a.moments()
+    for it in (3, 5):
+        want = R.filtered_frame(sums, m2, a.tiles, scales_of(a), W, H, it, 4.0)
+        assert np.array_equal(u32(a.resolve(denoise=dict(iterations=it))), u32(want)), it
+    # ... and they differ from the full frame's wherever the footprint crosses the set's edge
+    full = accumulator(s, W, H, PASSES)
+    whole = unpack(full, full.resolve(denoise=DENOISE), W, H)
+    assert not np.array_equal(a.resolve(denoise=DENOISE), R.pack(whole, a.tiles))
+    a.close()
+    full.close()
+
+
+@pytest.mark.gpu
+def test_overlapping_tiles_are_unsupported(scene):
+    s = scene("random")
+    a = accumulator(s, W, H, PASSES, tiles=[(0, 0, 20, 20), (16, 16, 20, 20)])
+    px = a.resolve()
+    for _ in range(2):
+        with pytest.raises(hrt.HrtError) as e:
+            a.resolve(denoise=True)
+        assert e.value.status == hrt.ERR_UNSUPPORTED
+    assert np.array_equal(u32(a.resolve()), u32(px))
+    a.close()
+
+
+# ------------------------------------------------------------------------------------------ 3. quality
+_ref = {}
+
+
+def cornell_reference(earth):
+    if "cornell" not in _ref:
+        rgb, _ = O.OracleScene(hrt.PRESETS["cornell"], 1, earth).render(32, 32, 4096, 50, seed=1234)
+        _ref["cornell"] = np.asarray(rgb[..., :3], np.float64)
+    return _ref["cornell"]
+
+
+@pytest.mark.gpu
+def test_filter_brings_a_noisy_cornell_closer_to_the_converged_frame(scene, earth):
+    """`cornell` at 32x32 in 16-px tiles after passes (0, 40) and (40, 80): the RMSE in display units against the
+    oracle's 4096-spp frame of another seed.  The oracle's own chunk sums give filtered / plain = 0.56 - 0.57 for this
+    input; 0.75 leaves room for the library's chunk schedule and f32 moments."""
+    s = scene("cornell")
+    a = accumulator(s, 32, 32, [(0, 40), (40, 80)])
+    ref = cornell_reference(earth)
+    plain = unpack(a, a.resolve(), 32, 32)[..., :3].astype(np.float64)
+    filt = unpack(a, a.resolve(denoise=dict(iterations=3, sigma=4)), 32, 32)[..., :3].astype(np.float64)
+    assert np.isfinite(filt).all()
+    rmse_plain, rmse_filt = np.sqrt(((plain - ref) ** 2).mean()), np.sqrt(((filt - ref) ** 2).mean())
+    print(f"\ncornell 32x32 at 80 spp: RMSE plain {rmse_plain:.4f}, filtered {rmse_filt:.4f}, ratio {rmse_filt / rmse_plain:.3f}")
+    assert rmse_filt / rmse_plain <= 0.75
+    a.close()
+
+
+# ------------------------------------------------------------------------------------------ 4. errors
+def _raises(status, fn):
+    with pytest.raises(hrt.HrtError) as e:
+        fn()
+    assert e.value.status == status, e.value
+
+
+@pytest.mark.gpu
+def test_errors_change_nothing(scene):
+    s = scene("random")
+    a = accumulator(s, W, H, [(0, 40)])
+    plain = accumulator(s, W, H, [(0, 40)], noise=False)
+    one = accumulator(s, W, H, [(0, 16)])                 # one 16-spp pass: K = 1
+    empty = hrt.Accumulator(s, W, H, hrt.tile_grid(W, H, 16), noise=True)
+    assert [r.chunks for r in one.noise(FLOOR)] == [1] * 12 and a.noise(FLOOR)[0].chunks >= 2
+    state = {x: (x.download()[0], x.resolve()) for x in (a, plain, one)}
+    m2 = {x: x.moments() for x in (a, one)}
+
+    def unchanged():
+        for x, (sums, px) in state.items():
+            assert np.array_equal(u32(x.download()[0]), u32(sums)) and np.array_equal(u32(x.resolve()), u32(px))
+        for x, m in m2.items():
+            assert np.array_equal(u32(x.moments()), u32(m))
+        assert a.samples == plain.samples == 40 and one.samples == 16 and empty.samples == 0
+
+    for fmt in ("f32", "rgba8"):
+        _raises(hrt.ERR_STATE, lambda: plain.resolve(fmt, denoise=True))       # created without the plane
+        _raises(hrt.ERR_STATE, lambda: one.resolve(fmt, denoise=True))         # K = 1: no variance estimate
+        _raises(hrt.ERR_STATE, lambda: empty.resolve(fmt, denoise=True))       # no samples
+    for it in (0, 6):
+        _raises(hrt.ERR_INVALID_ARG, lambda: a.resolve(denoise=dict(iterations=it)))
+    for sigma in (0.0, -4.0, float("nan")):
+        _raises(hrt.ERR_INVALID_ARG, lambda: a.resolve(denoise=dict(sigma=sigma)))
+    # argument errors come first, also on an accumulator that could not be filtered
+    _raises(hrt.ERR_INVALID_ARG, lambda: plain.resolve(denoise=dict(iterations=0)))
+    L, f = hrt.load(), hrt.filter_params()
+    out = np.zeros(W * H * 4, F)
+    import ctypes
+    assert L.hrt_accum_resolve_filtered_host(a.h, None, hrt.ACCUM_F32, out.ctypes.data) == hrt.ERR_INVALID_ARG
+    assert L.hrt_accum_resolve_filtered_host(a.h, ctypes.byref(f), hrt.ACCUM_F32, None) == hrt.ERR_INVALID_ARG
+    assert L.hrt_accum_resolve_filtered_host(a.h, ctypes.byref(f), 2, out.ctypes.data) == hrt.ERR_INVALID_ARG
+    assert L.hrt_accum_resolve_filtered(a.h, ctypes.byref(f), hrt.ACCUM_F32, None, None) == hrt.ERR_INVALID_ARG
+    assert not out.any()
+    unchanged()
+    # a tile with one chunk among tiles with more: still no estimate for that tile
+    one.add(*setup(s, W, H, 16, offset=16), tiles=[0, 1])
+    _raises(hrt.ERR_STATE, lambda: one.resolve(denoise=True))
+    one.add(*setup(s, W, H, 16, offset=16), tiles=list(range(2, 12)))
+    assert one.resolve(denoise=True).shape == (W * H, 4)
+    a.resolve(denoise=True)
+    for x in (a, plain, one, empty):
+        x.close()
+
+
+@pytest.mark.gpu
+def test_filtered_resolve_on_a_stream_into_device_memory(scene):
+    """hrt_accum_resolve_filtered itself: torch's current stream, a device buffer, twice into the same planes."""
+    import ctypes
+
+    import torch
+
+    s = scene("random")
+    a = accumulator(s, W, H, PASSES)
+    want = a.resolve(denoise=DENOISE)
+    f = hrt.filter_params(**DENOISE)
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        for _ in range(2):
+            buf = torch.zeros(W * H * 4, dtype=torch.float32, device="cuda")
+            st = hrt.load().hrt_accum_resolve_filtered(a.h, ctypes.byref(f), hrt.ACCUM_F32, ctypes.c_void_p(buf.data_ptr()),
+                                                       ctypes.c_void_p(stream.cuda_stream))
+            assert st == hrt.OK
+            stream.synchronize()
+            assert np.array_equal(u32(buf.cpu().numpy().reshape(-1, 4)), u32(want))
+    a.close()
