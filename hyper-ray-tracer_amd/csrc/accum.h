@@ -1,6 +1,6 @@
 /*
  * accum.h — the arithmetic of the sample accumulator (hrt_accum, include/hrt/hrt.h), the same code on the
- * device (render.hip accumulate_chunks / accum_merge / accum_resolve) and on the host (hrt_debug_accumulate
+ * device (accum.hip accumulate_chunks / accum_merge / accum_resolve) and on the host (hrt_debug_accumulate
  * with on_device = 0), like hd_math.h and lane.h: built with -ffp-contract=off, f32 '/' and sqrt IEEE
  * correctly rounded on both sides, so the two give the same bits.
  *

@@ -1,0 +1,872 @@
+/*
+ * accum.hip — the sample accumulator (hrt_accum, include/hrt/hrt.h): its streaming kernels (arithmetic: accum.h), host
+ * state and entry points.  A pass is render.hip's render_launch, which ends in launch_accumulate{,_mapped} below; the
+ * samples and chunks each tile then holds are accum_ledger.h's book; the filtered resolve's kernels are filter.hip's.
+ */
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <type_traits>
+#include <vector>
+
+#include "accum.h"
+#include "accum_ledger.h"
+#include "filter.h"
+#include "render_host.h"
+
+using namespace hrt;
+using namespace hrt::lane;
+using namespace hrt::kern;
+
+namespace {
+
+/* ---- the kernels.  Plain streaming kernels: a grid-stride loop over pixels, one 16-B load or store per lane and
+ * array (consecutive lanes, consecutive float4s). */
+/* a resolved pixel to out[i]: RGBA f32 with alpha 1, or 4 x u8 with alpha 255 */
+template <int FORMAT>
+__host__ __device__ inline void store_resolved(void* out, size_t i, Vec3 acc, float scale) {
+  const Vec3 px = accum::resolve_f32(acc, scale);
+  if constexpr (FORMAT == HRT_ACCUM_F32) static_cast<float4*>(out)[i] = make_float4(px.x, px.y, px.z, 1.0f);
+  else static_cast<uint32_t*>(out)[i] = accum::resolve_rgba8(px);
+}
+
+/* acc[i] += the pass sum of partial[.][i]; FORMAT >= 0: the frame after the pass goes to out in the same trip
+ * (scale = 1 / the samples then held), so a preview after every pass is this one kernel after the megakernel */
+template <int FORMAT>
+__host__ __device__ inline void accumulate_pixel(const float4* partial, float4* acc, size_t n, uint32_t n_chunks, float scale,
+                                                 void* out, size_t i) {
+  const float4 a = acc[i];
+  const Vec3 sum = accum::add_pass(v3(a.x, a.y, a.z), accum::pass_sum(partial, n_chunks, n, i));
+  acc[i] = make_float4(sum.x, sum.y, sum.z, 0.0f);
+  if constexpr (FORMAT >= 0) store_resolved<FORMAT>(out, i, sum, scale);
+}
+/* the samples of a pass's chunk c: lane.h chunk_range on the pass's schedule (the function the render kernels split
+ * a pixel's samples by), or the caller's table (hrt_debug_noise) */
+struct ChunkCounts {
+  const uint32_t* sizes; /* null: the schedule below */
+  uint32_t chunk, chunk_head, chunk_first;
+  __host__ __device__ uint32_t operator()(uint32_t c) const {
+    if (sizes) return sizes[c];
+    KParams P; /* chunk_range reads these three fields alone */
+    P.chunk = chunk;
+    P.chunk_head = chunk_head;
+    P.chunk_first = chunk_first;
+    uint32_t s0, s1;
+    chunk_range(P, c, s0, s1);
+    return s1 - s0;
+  }
+};
+/* What accumulate_chunks<FORMAT, true> takes beyond the plain kernel's arguments: the noise plane and the tile map.
+ * The map is the launch's own tile table: per launched tile out_off = the source offset in the launch's packed sums,
+ * acc_off = the destination offset in the accumulator, w * h = the pixel count, so a pass over a subset of an
+ * accumulator's tiles is one megakernel launch and this one kernel. */
+template <bool MOMENTS>
+struct MomentArgs {};
+template <>
+struct MomentArgs<true> {
+  float* m2; /* n_px f32 packed as acc (accum.h pass_moment / add_moment); null: the accumulator keeps none */
+  const G::TileDev* tiles;
+  uint32_t n_tiles;
+  ChunkCounts counts;
+};
+/* launch pixel i -> its pixel in the accumulator: the last tile whose out_off <= i */
+__host__ __device__ inline size_t mapped_pixel(const G::TileDev* tiles, uint32_t n_tiles, size_t i) {
+  uint32_t lo = 0, hi = n_tiles;
+  while (hi - lo > 1u) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (tiles[mid].out_off <= i) lo = mid;
+    else hi = mid;
+  }
+  return (size_t)tiles[lo].acc_off + (i - tiles[lo].out_off);
+}
+template <int FORMAT>
+__host__ __device__ inline void accumulate_pixel_mapped(const float4* partial, float4* acc, size_t n, uint32_t n_chunks, float scale,
+                                                        void* out, size_t i, const MomentArgs<true>& M) {
+  const size_t d = mapped_pixel(M.tiles, M.n_tiles, i);
+  const float4 a = acc[d];
+  const Vec3 sum = accum::add_pass(v3(a.x, a.y, a.z), accum::pass_sum(partial, n_chunks, n, i));
+  acc[d] = make_float4(sum.x, sum.y, sum.z, 0.0f);
+  if (M.m2) M.m2[d] = accum::add_moment(M.m2[d], accum::pass_moment(partial, n_chunks, n, i, M.counts));
+  if constexpr (FORMAT >= 0) store_resolved<FORMAT>(out, d, sum, scale);
+}
+template <int FORMAT, bool MOMENTS = false>
+__global__ __launch_bounds__(256) void accumulate_chunks(const float4* __restrict__ partial, float4* __restrict__ acc, size_t n,
+                                                         uint32_t n_chunks, float scale, void* __restrict__ out,
+                                                         MomentArgs<MOMENTS> M) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    if constexpr (MOMENTS) accumulate_pixel_mapped<FORMAT>(partial, acc, n, n_chunks, scale, out, i, M);
+    else accumulate_pixel<FORMAT>(partial, acc, n, n_chunks, scale, out, i);
+  }
+}
+
+/* dst += src */
+__global__ __launch_bounds__(256) void accum_merge(float4* __restrict__ dst, const float4* __restrict__ src, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const float4 a = dst[i], b = src[i];
+    const Vec3 sum = accum::add_pass(v3(a.x, a.y, a.z), v3(b.x, b.y, b.z));
+    dst[i] = make_float4(sum.x, sum.y, sum.z, 0.0f);
+  }
+}
+/* ... of the noise planes */
+__global__ __launch_bounds__(256) void accum_merge_m2(float* __restrict__ dst, const float* __restrict__ src, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    dst[i] = accum::add_moment(dst[i], src[i]);
+}
+
+/* One tile of an accumulator as accum_noise and accum_resolve_tiles see it: its pixels [off, off + n) of the packed
+ * order, and the scales of the samples and chunks it holds. */
+struct alignas(16) NoiseTile {
+  uint32_t off, n;
+  float inv_n;  /* accum::resolve_scale(samples) */
+  float inv_k1; /* accum::chunks_scale(chunks) */
+  uint32_t few; /* fewer than 2 chunks: no estimate */
+  uint32_t pad[3];
+};
+/* The error of every pixel of a tile (optionally stored to err, packed as acc) reduced to the tile's mean and max:
+ * one workgroup of 256 per tile, the fixed order of accum.h tile_reduce. */
+__global__ __launch_bounds__(accum::NOISE_BLOCK) void accum_noise(const float4* __restrict__ acc, const float* __restrict__ m2,
+                                                                  const NoiseTile* __restrict__ tiles, float floor,
+                                                                  float* __restrict__ err, float2* __restrict__ out) {
+  __shared__ float sh_s[accum::NOISE_BLOCK], sh_m[accum::NOISE_BLOCK];
+  const NoiseTile T = tiles[blockIdx.x];
+  const uint32_t j = threadIdx.x;
+  float s = 0.0f, m = 0.0f;
+  for (uint32_t k = j; k < T.n; k += accum::NOISE_BLOCK) {
+    const size_t d = (size_t)T.off + k;
+    const float4 a = acc[d];
+    const float e = accum::noise_err(v3(a.x, a.y, a.z), m2[d], T.inv_n, T.inv_k1, T.few != 0u, floor);
+    if (err) err[d] = e;
+    s = s + e;
+    m = accum::larger(m, e);
+  }
+  sh_s[j] = s;
+  sh_m[j] = m;
+  __syncthreads();
+  if (j < 128u) { /* s = 128, across waves */
+    s = s + sh_s[j + 128u];
+    m = accum::larger(m, sh_m[j + 128u]);
+  }
+  __syncthreads();
+  if (j < 128u) {
+    sh_s[j] = s;
+    sh_m[j] = m;
+  }
+  __syncthreads();
+  if (j < 64u) { /* s = 64 across waves, then 32 ... 1 inside wave 0: lane j takes lane j + s's value */
+    s = s + sh_s[j + 64u];
+    m = accum::larger(m, sh_m[j + 64u]);
+    for (int off = 32; off >= 1; off >>= 1) {
+      s = s + __shfl_down(s, off);
+      m = accum::larger(m, __shfl_down(m, off));
+    }
+    if (j == 0u) out[blockIdx.x] = make_float2(s * (1.0f / (float)T.n), m);
+  }
+}
+
+template <int FORMAT>
+__global__ __launch_bounds__(256) void accum_resolve(const float4* __restrict__ acc, size_t n, float scale, void* __restrict__ out) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const float4 a = acc[i];
+    store_resolved<FORMAT>(out, i, v3(a.x, a.y, a.z), scale);
+  }
+}
+/* ... of an accumulator whose tiles hold different sample counts: tile t resolves with its own 1 / N_t.  A
+ * workgroup per tile (further tiles in further trips), its lanes over the tile's consecutive pixels. */
+template <int FORMAT>
+__global__ __launch_bounds__(256) void accum_resolve_tiles(const float4* __restrict__ acc, const NoiseTile* __restrict__ tiles,
+                                                           uint32_t n_tiles, void* __restrict__ out) {
+  for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    const NoiseTile T = tiles[t];
+    for (uint32_t k = threadIdx.x; k < T.n; k += blockDim.x) {
+      const size_t d = (size_t)T.off + k;
+      const float4 a = acc[d];
+      store_resolved<FORMAT>(out, d, v3(a.x, a.y, a.z), T.inv_n);
+    }
+  }
+}
+
+/* ---- the launches.  f(std::integral_constant<int, FORMAT>{}) for the HRT_ACCUM_* format; NONE: with FORMAT = -1, no resolved output,
+ * for any other value, which otherwise the entry points have refused (accum_format) */
+template <bool NONE = false, class F>
+void with_format(int format, F&& f) {
+  if (format == HRT_ACCUM_F32) f(std::integral_constant<int, HRT_ACCUM_F32>{});
+  else if (format == HRT_ACCUM_RGBA8 || !NONE) f(std::integral_constant<int, HRT_ACCUM_RGBA8>{});
+  else if constexpr (NONE) f(std::integral_constant<int, -1>{});
+}
+
+template <bool MOMENTS>
+void accumulate(int format, const float4* partial, float4* acc, size_t n, uint32_t n_chunks, float scale, void* out,
+                const MomentArgs<MOMENTS>& M, hipStream_t stream) {
+  with_format<true>(format, [&](auto fc) {
+    constexpr int F = decltype(fc)::value;
+    hipLaunchKernelGGL((accumulate_chunks<F, MOMENTS>), dim3(stream_blocks(n)), dim3(256), 0, stream, partial, acc, n, n_chunks,
+                       F < 0 ? 0.0f : scale, F < 0 ? nullptr : out, M);
+  });
+  hip_check(hipGetLastError(), "accumulate_chunks launch");
+}
+void resolve_pixels(int32_t format, const float4* acc, size_t n, float scale, void* d_out, hipStream_t stream) {
+  with_format(format, [&](auto fc) {
+    hipLaunchKernelGGL((accum_resolve<decltype(fc)::value>), dim3(stream_blocks(n)), dim3(256), 0, stream, acc, n, scale, d_out);
+  });
+  hip_check(hipGetLastError(), "accum_resolve launch");
+}
+
+/* what makes two passes samples of the same frame: everything of (camera, params) but samples and sample_offset */
+struct FrameIdentity {
+  hrt_camera cam;
+  uint32_t width, height, max_depth, flags;
+  float t_min, background[3];
+  uint64_t seed;
+};
+FrameIdentity frame_identity(const hrt_camera* cam, const hrt_render_params* p) {
+  FrameIdentity id;
+  memset(&id, 0, sizeof(id));
+  id.cam = *cam;
+  id.width = p->width;
+  id.height = p->height;
+  id.max_depth = p->max_depth;
+  id.flags = p->flags;
+  id.t_min = p->t_min;
+  for (int k = 0; k < 3; k++) id.background[k] = p->background[k];
+  id.seed = p->seed;
+  return id;
+}
+bool same_identity(const FrameIdentity& a, const FrameIdentity& b) {
+  return memcmp(&a.cam, &b.cam, sizeof(hrt_camera)) == 0 && a.width == b.width && a.height == b.height &&
+         a.max_depth == b.max_depth && a.flags == b.flags && memcmp(&a.t_min, &b.t_min, sizeof(float)) == 0 &&
+         memcmp(a.background, b.background, sizeof(a.background)) == 0 && a.seed == b.seed;
+}
+
+}  // namespace
+
+void hrt::launch_accumulate(int format, const float4* partial, float4* acc, size_t n, uint32_t n_chunks, float scale, void* out,
+                            hipStream_t stream) {
+  accumulate(format, partial, acc, n, n_chunks, scale, out, MomentArgs<false>{}, stream);
+}
+void hrt::launch_accumulate_mapped(int format, const float4* partial, float4* acc, size_t n, uint32_t n_chunks, float scale, void* out,
+                                   float* m2, const gpu::TileDev* tiles, uint32_t n_tiles, uint32_t chunk, uint32_t chunk_head,
+                                   uint32_t chunk_first, hipStream_t stream) {
+  const MomentArgs<true> M{m2, tiles, n_tiles, ChunkCounts{nullptr, chunk, chunk_head, chunk_first}};
+  accumulate(format, partial, acc, n, n_chunks, scale, out, M, stream);
+}
+
+struct hrt_accum {
+  hrt_scene* scene = nullptr;
+  int device = -1;
+  uint32_t width = 0, height = 0;
+  std::vector<hrt_tile> tiles;
+  size_t n_px = 0;
+  float4* d_acc = nullptr; /* n_px raw sums (x, y, z; w = 0), packed as the tiles are */
+  bool has_identity = false;
+  FrameIdentity identity;
+  AccumLedger ledger; /* the samples and chunks (K) every tile holds */
+  bool invalid = false; /* a pass was stopped by the walk watchdog: the sums are incomplete until a reset */
+  float* d_m2 = nullptr;   /* HRT_ACCUM_NOISE: n_px moments (accum.h), packed as d_acc */
+  std::vector<uint32_t> tile_off; /* first pixel of each tile in the packed order */
+  NoiseTile* d_ntiles = nullptr; /* n_tiles records for accum_noise / accum_resolve_tiles, and their host copy */
+  float2* d_nout = nullptr;      /* n_tiles x (mean, max) */
+  std::vector<NoiseTile> h_ntiles;
+  /* The filtered resolve's buffers (filter.h), made by the first hrt_accum_resolve_filtered: two raster planes over
+   * the tiles' bounding box and the tiles in plane coordinates.  f_state: 0 not made yet, 1 made, -1 the tiles overlap */
+  int f_state = 0;
+  uint32_t f_w = 0, f_h = 0, f_blocks = 0;
+  float4* d_fplane[2] = {nullptr, nullptr};
+  filter::FilterTile* d_ftiles = nullptr;
+  std::vector<filter::FilterTile> h_ftiles;
+};
+
+namespace {
+
+void accum_usable(const hrt_accum* a) {
+  if (a->invalid) throw HipError{HRT_ERR_STATE, "the accumulator holds an incomplete pass (walk watchdog): reset it"};
+}
+void accum_format(int32_t format) {
+  if (format != HRT_ACCUM_F32 && format != HRT_ACCUM_RGBA8) throw HipError{HRT_ERR_INVALID_ARG, "unknown HRT_ACCUM_* format"};
+}
+void check_identity(const hrt_accum* a, const FrameIdentity& id) {
+  if (id.width != a->width || id.height != a->height)
+    throw HipError{HRT_ERR_INVALID_ARG, "the params' width and height are not the accumulator's"};
+  if (a->has_identity && !same_identity(a->identity, id))
+    throw HipError{HRT_ERR_INVALID_ARG, "another frame identity (camera, max_depth, flags, t_min, background, seed) than the accumulator's"};
+}
+void check_range(AccumLedger::Refusal why) {
+  if (why == AccumLedger::BAD_RANGE) throw HipError{HRT_ERR_INVALID_ARG, "empty sample range, or one that ends past 2^32"};
+  if (why == AccumLedger::OVERLAP) throw HipError{HRT_ERR_INVALID_ARG, "the sample range overlaps samples the accumulator holds"};
+}
+void accum_uniform(const hrt_accum* a, hrt_status st, const char* what) {
+  if (!a->ledger.uniform()) throw HipError{st, what};
+}
+void accum_holds_samples(const hrt_accum* a) {
+  if (a->ledger.empty()) throw HipError{HRT_ERR_STATE, "the accumulator holds no samples"};
+}
+/* the record of n pixels from `off` on that hold `samples` samples in `chunks` chunks */
+NoiseTile noise_tile(uint32_t off, uint32_t n, uint64_t samples, uint64_t chunks) {
+  NoiseTile T;
+  memset(&T, 0, sizeof(T));
+  T.off = off;
+  T.n = n;
+  T.inv_n = samples ? accum::resolve_scale(samples) : 0.0f;
+  T.few = chunks < 2 ? 1u : 0u;
+  T.inv_k1 = chunks < 2 ? 0.0f : accum::chunks_scale(chunks);
+  return T;
+}
+/* the records accum_noise and accum_resolve_tiles read, from the ledger, onto the device (stream-ordered; h_ntiles
+ * stays alive with the accumulator) */
+void upload_noise_tiles(hrt_accum* a, hipStream_t stream) {
+  const size_t nt = a->tiles.size();
+  a->h_ntiles.resize(nt);
+  for (size_t t = 0; t < nt; t++)
+    a->h_ntiles[t] = noise_tile(a->tile_off[t], a->tiles[t].w * a->tiles[t].h, a->ledger.samples(t), a->ledger.chunks(t));
+  hip_check(hipMemcpyAsync(a->d_ntiles, a->h_ntiles.data(), nt * sizeof(NoiseTile), hipMemcpyHostToDevice, stream),
+            "hipMemcpyAsync(noise tiles)");
+}
+/* tiles that hold different sample counts resolve each with its own (accum_resolve_tiles); every tile needs samples */
+void launch_resolve_tiles(hrt_accum* a, int32_t format, void* d_out, hipStream_t stream) {
+  const uint32_t nt = (uint32_t)a->tiles.size(), blocks = std::min(nt, STREAM_MAX_BLOCKS);
+  for (uint32_t t = 0; t < nt; t++)
+    if (a->ledger.samples(t) == 0) throw HipError{HRT_ERR_STATE, "a tile of the accumulator holds no samples"};
+  upload_noise_tiles(a, stream);
+  with_format(format, [&](auto fc) {
+    hipLaunchKernelGGL((accum_resolve_tiles<decltype(fc)::value>), dim3(blocks), dim3(256), 0, stream, (const float4*)a->d_acc,
+                       (const NoiseTile*)a->d_ntiles, nt, d_out);
+  });
+  hip_check(hipGetLastError(), "accum_resolve_tiles launch");
+}
+void launch_resolve(hrt_accum* a, int32_t format, void* d_out, hipStream_t stream) {
+  if (!a->ledger.uniform()) return launch_resolve_tiles(a, format, d_out, stream);
+  resolve_pixels(format, a->d_acc, a->n_px, accum::resolve_scale(a->ledger.samples(0)), d_out, stream);
+}
+
+/* hrt_accum_resolve_filtered's checks: nothing changes on an error */
+void filter_args(const hrt_filter_params* f) {
+  if (f->iterations < 1 || f->iterations > filter::MAX_ITERATIONS)
+    throw HipError{HRT_ERR_INVALID_ARG, "hrt_filter_params: iterations outside [1, 5]"};
+  if (!(f->sigma > 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_filter_params: sigma must be > 0"};
+}
+void filter_state(const hrt_accum* a) {
+  accum_usable(a);
+  if (!a->d_m2) throw HipError{HRT_ERR_STATE, "hrt_accum_resolve_filtered: the accumulator was created without HRT_ACCUM_NOISE"};
+  accum_holds_samples(a);
+  for (size_t t = 0; t < a->tiles.size(); t++)
+    if (a->ledger.samples(t) == 0 || a->ledger.chunks(t) < 2)
+      throw HipError{HRT_ERR_STATE, "hrt_accum_resolve_filtered: a tile holds no samples or fewer than 2 chunks (no variance estimate)"};
+}
+/* the planes and the tile records, once per accumulator: its tiles never change */
+void filter_prepare(hrt_accum* a, hipStream_t stream) {
+  if (a->f_state < 0) throw HipError{HRT_ERR_UNSUPPORTED, "hrt_accum_resolve_filtered: the accumulator's tiles overlap"};
+  if (a->f_state > 0) return;
+  uint32_t x0 = UINT32_MAX, y0 = UINT32_MAX, x1 = 0, y1 = 0;
+  for (const hrt_tile& t : a->tiles) {
+    x0 = std::min(x0, t.x), y0 = std::min(y0, t.y);
+    x1 = std::max(x1, t.x + t.w), y1 = std::max(y1, t.y + t.h);
+  }
+  const uint32_t w = x1 - x0, h = y1 - y0;
+  const size_t area = (size_t)w * h;
+  /* disjoint tiles cover as many pixels as they hold */
+  std::vector<bool> covered(area, false);
+  for (const hrt_tile& t : a->tiles)
+    for (uint32_t y = t.y - y0; y < t.y - y0 + t.h; y++)
+      for (uint32_t x = t.x - x0; x < t.x - x0 + t.w; x++) {
+        if (covered[(size_t)y * w + x]) {
+          a->f_state = -1;
+          throw HipError{HRT_ERR_UNSUPPORTED, "hrt_accum_resolve_filtered: the accumulator's tiles overlap"};
+        }
+        covered[(size_t)y * w + x] = true;
+      }
+  std::vector<filter::FilterTile> ft(a->tiles.size());
+  uint64_t blocks = 0;
+  for (size_t t = 0; t < ft.size(); t++) {
+    const hrt_tile& T = a->tiles[t];
+    ft[t] = filter::FilterTile{T.x - x0, T.y - y0, T.w, T.h, a->tile_off[t], (uint32_t)blocks, 0.0f, 0.0f};
+    blocks += filter::tile_blocks(T.w, T.h);
+  }
+  if (blocks >= (1ull << 31)) throw HipError{HRT_ERR_UNSUPPORTED, "hrt_accum_resolve_filtered: too many tile blocks for one launch"};
+  float4* plane[2] = {nullptr, nullptr};
+  filter::FilterTile* d_ft = nullptr;
+  try {
+    for (float4*& pl : plane) hip_check(hipMalloc((void**)&pl, area * sizeof(float4)), "hipMalloc(filter plane)");
+    hip_check(hipMalloc((void**)&d_ft, ft.size() * sizeof(filter::FilterTile)), "hipMalloc(filter tiles)");
+    /* pixels no tile covers are absent: v < 0 (0xBFBFBFBF is -1.498).  filter_gather writes the covered ones of
+     * plane 0 alone and every iteration passes absent pixels on, so once is enough; it is waited for, so that a
+     * later resolve on another stream finds it done */
+    if (a->n_px != area) {
+      hip_check(hipMemsetAsync(plane[0], 0xBF, area * sizeof(float4), stream), "hipMemsetAsync(filter plane)");
+      hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize(filter plane)");
+    }
+  } catch (...) {
+    for (float4* pl : plane)
+      if (pl) (void)hipFree(pl);
+    if (d_ft) (void)hipFree(d_ft);
+    throw;
+  }
+  a->d_fplane[0] = plane[0], a->d_fplane[1] = plane[1];
+  a->d_ftiles = d_ft;
+  a->h_ftiles.swap(ft);
+  a->f_w = w, a->f_h = h, a->f_blocks = (uint32_t)blocks;
+  a->f_state = 1;
+}
+void launch_filtered(hrt_accum* a, const hrt_filter_params* f, int32_t format, void* d_out, hipStream_t stream) {
+  filter_prepare(a, stream);
+  upload_noise_tiles(a, stream); /* each tile's own 1 / N and 1 / (K - 1) */
+  const uint32_t nt = (uint32_t)a->tiles.size();
+  for (uint32_t t = 0; t < nt; t++) {
+    a->h_ftiles[t].inv_n = a->h_ntiles[t].inv_n;
+    a->h_ftiles[t].inv_k1 = a->h_ntiles[t].inv_k1;
+  }
+  hip_check(hipMemcpyAsync(a->d_ftiles, a->h_ftiles.data(), nt * sizeof(filter::FilterTile), hipMemcpyHostToDevice, stream),
+            "hipMemcpyAsync(filter tiles)");
+  filter::launch_gather(a->d_acc, a->d_m2, a->d_ftiles, nt, a->f_blocks, a->d_fplane[0], a->f_w, stream);
+  filter::launch_atrous(a->d_fplane[0], a->d_fplane[1], a->f_w, a->f_h, a->d_ftiles, nt, a->f_blocks, f->iterations, f->sigma,
+                        format, d_out, stream);
+}
+
+/* hrt_accum_resolve_host / _filtered_host after their checks: `launch` resolves into a buffer of the scene's pool on
+ * the null stream, once the passes the caller queued on any stream are done, and the buffer is copied to out */
+template <class Launch>
+void resolve_to_host(hrt_accum* a, int32_t format, void* out, const char* copy, Launch&& launch) {
+  DeviceGuard dg(a->device);
+  struct PoolBuf {
+    hrt_scene* scene;
+    OutBuf b;
+    ~PoolBuf() { out_pool_give(scene, b); }
+  } buf{a->scene, out_pool_take(a->scene, a->n_px * 16 + 16)};
+  hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+  launch(buf.b.ptr);
+  hip_check(hipMemcpy(out, buf.b.ptr, a->n_px * (format == HRT_ACCUM_F32 ? 16u : 4u), hipMemcpyDeviceToHost), copy);
+}
+
+/* K of a pass: the chunks its schedule sums a pixel's samples in */
+uint64_t pass_chunks(const hrt_scene* s, const hrt_render_params* p) {
+  uint32_t chunk = 0, n_head = 0, first = 0, n_tail = 0;
+  chunk_schedule(s, p, chunk, n_head, first, n_tail);
+  return (uint64_t)n_head + n_tail;
+}
+
+/* A pass into every tile (idx null: hrt_accum_add, hrt_accum_add_resolve) or into tiles[idx[0..n)] alone
+ * (hrt_accum_add_tiles): checks first (nothing changes on an error), then the shared launch */
+void accum_add(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, const uint32_t* idx, uint32_t n, int32_t format,
+               void* d_out, void* stream, hrt_render_stats* stats) {
+  accum_usable(a);
+  if (d_out) accum_uniform(a, HRT_ERR_UNSUPPORTED, "hrt_accum_add_resolve: the accumulator's tiles hold different passes");
+  const size_t nt = a->tiles.size();
+  std::vector<uint8_t> taken(idx ? nt : 0, 0);
+  std::vector<hrt_tile> sub; /* the launch's tiles and where each lands in the accumulator */
+  std::vector<uint32_t> offs;
+  for (uint32_t i = 0; idx && i < n; i++) {
+    if (idx[i] >= nt || taken[idx[i]]) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_add_tiles: a tile index out of range or given twice"};
+    taken[idx[i]] = 1;
+    sub.push_back(a->tiles[idx[i]]);
+    offs.push_back(a->tile_off[idx[i]]);
+  }
+  const FrameIdentity id = frame_identity(cam, p);
+  check_identity(a, id);
+  const SampleRange r{p->sample_offset, (uint64_t)p->sample_offset + p->samples};
+  if (p->samples != 0) check_range(a->ledger.may_add(r, idx, n)); /* samples = 0: check_render_args reports it */
+  SumsDest dst;
+  dst.d_acc = a->d_acc;
+  dst.d_m2 = a->d_m2;
+  /* a subset always takes the mapped kernel (launched tile i is the accumulator's tile idx[i]); the whole frame only
+   * with a noise plane: without, the plain kernel, as ever (the tiles map onto themselves) */
+  dst.mapped = idx || a->d_m2;
+  dst.acc_offs = idx ? offs.data() : nullptr;
+  if (d_out) { /* the whole frame of a uniform accumulator: every tile holds samples(0) */
+    dst.preview = format;
+    dst.d_preview = d_out;
+    dst.preview_scale = accum::resolve_scale(a->ledger.samples(0) + p->samples);
+  }
+  bool launched = false;
+  try {
+    render_launch(a->scene, cam, p, idx ? sub.data() : a->tiles.data(), idx ? n : (uint32_t)nt, dst, stream, stats, &launched);
+  } catch (...) {
+    if (launched) a->invalid = true; /* the pass is (partly) in the sums and cannot be taken out again */
+    throw;
+  }
+  a->identity = id;
+  a->has_identity = true;
+  a->ledger.record(r, pass_chunks(a->scene, p), idx, n);
+}
+
+}  // namespace
+
+extern "C" {
+
+hrt_status hrt_accum_create(hrt_scene* s, uint32_t width, uint32_t height, const hrt_tile* tiles, uint32_t n_tiles,
+                            hrt_accum** out) {
+  return hrt_accum_create_ex(s, width, height, tiles, n_tiles, 0, out);
+}
+
+hrt_status hrt_accum_create_ex(hrt_scene* s, uint32_t width, uint32_t height, const hrt_tile* tiles, uint32_t n_tiles,
+                               uint32_t flags, hrt_accum** out) {
+  return hguard([&] {
+    if (!s || !tiles || !out || n_tiles == 0) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_create: null argument or no tiles"};
+    *out = nullptr;
+    if (flags & ~(uint32_t)HRT_ACCUM_NOISE) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_create_ex: unknown flag"};
+    if (width < 2 || height < 2 || width > 65535 || height > 65535)
+      throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_create: 2 <= width, height <= 65535"};
+    uint64_t n_px = 0;
+    for (uint32_t i = 0; i < n_tiles; i++) {
+      const hrt_tile& t = tiles[i];
+      if (t.w == 0 || t.h == 0 || (uint64_t)t.x + t.w > width || (uint64_t)t.y + t.h > height)
+        throw HipError{HRT_ERR_INVALID_ARG, "tile outside the image"};
+      n_px += (uint64_t)t.w * t.h;
+    }
+    if (n_px >= (1ull << 32)) throw HipError{HRT_ERR_UNSUPPORTED, "more than 2^32 pixels in one accumulator"};
+    if (!s->committed || !s->d_blob) throw HipError{HRT_ERR_STATE, "scene not committed"};
+    DeviceGuard dg(s->device);
+    hrt_accum* a = new hrt_accum();
+    a->scene = s;
+    a->device = s->device;
+    a->width = width;
+    a->height = height;
+    a->tiles.assign(tiles, tiles + n_tiles);
+    a->n_px = (size_t)n_px;
+    a->ledger = AccumLedger(n_tiles);
+    a->tile_off.resize(n_tiles);
+    for (uint32_t i = 0, off = 0; i < n_tiles; i++) {
+      a->tile_off[i] = off;
+      off += tiles[i].w * tiles[i].h;
+    }
+    try {
+      hip_check(hipMalloc((void**)&a->d_acc, a->n_px * sizeof(float4)), "hipMalloc(accumulator)");
+      hip_check(hipMemset(a->d_acc, 0, a->n_px * sizeof(float4)), "hipMemset(accumulator)");
+      hip_check(hipMalloc((void**)&a->d_ntiles, n_tiles * sizeof(NoiseTile)), "hipMalloc(accumulator tiles)");
+      if (flags & HRT_ACCUM_NOISE) {
+        hip_check(hipMalloc((void**)&a->d_m2, a->n_px * sizeof(float)), "hipMalloc(noise plane)");
+        hip_check(hipMemset(a->d_m2, 0, a->n_px * sizeof(float)), "hipMemset(noise plane)");
+        hip_check(hipMalloc((void**)&a->d_nout, n_tiles * sizeof(float2)), "hipMalloc(noise records)");
+      }
+    } catch (...) {
+      hrt_accum_destroy(a);
+      throw;
+    }
+    *out = a;
+  });
+}
+
+void hrt_accum_destroy(hrt_accum* a) {
+  if (!a) return;
+  int prev = -1;
+  (void)hipGetDevice(&prev);
+  (void)hipSetDevice(a->device);
+  if (a->d_acc) (void)hipFree(a->d_acc); /* waits for the work that uses it */
+  if (a->d_m2) (void)hipFree(a->d_m2);
+  if (a->d_ntiles) (void)hipFree(a->d_ntiles);
+  if (a->d_nout) (void)hipFree(a->d_nout);
+  for (float4* plane : a->d_fplane)
+    if (plane) (void)hipFree(plane);
+  if (a->d_ftiles) (void)hipFree(a->d_ftiles);
+  if (prev >= 0) (void)hipSetDevice(prev);
+  delete a;
+}
+
+hrt_status hrt_accum_reset(hrt_accum* a, void* stream) {
+  return hguard([&] {
+    if (!a) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_reset: null accumulator"};
+    DeviceGuard dg(a->device);
+    hip_check(hipMemsetAsync(a->d_acc, 0, a->n_px * sizeof(float4), (hipStream_t)stream), "hipMemsetAsync(accumulator)");
+    if (a->d_m2) hip_check(hipMemsetAsync(a->d_m2, 0, a->n_px * sizeof(float), (hipStream_t)stream), "hipMemsetAsync(noise plane)");
+    a->ledger.clear();
+    a->has_identity = false;
+    a->invalid = false;
+  });
+}
+
+hrt_status hrt_accum_add(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, void* stream,
+                         hrt_render_stats* stats) {
+  return hguard([&] {
+    if (!a || !cam || !p) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_add: null argument"};
+    accum_add(a, cam, p, nullptr, 0, -1, nullptr, stream, stats);
+  });
+}
+
+hrt_status hrt_accum_add_resolve(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, int32_t format,
+                                 void* d_out, void* stream, hrt_render_stats* stats) {
+  return hguard([&] {
+    if (!a || !cam || !p || !d_out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_add_resolve: null argument"};
+    accum_format(format);
+    accum_add(a, cam, p, nullptr, 0, format, d_out, stream, stats);
+  });
+}
+
+hrt_status hrt_accum_samples(const hrt_accum* a, uint64_t* samples) {
+  return hguard([&] {
+    if (!a || !samples) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_samples: null argument"};
+    accum_uniform(a, HRT_ERR_STATE, "hrt_accum_samples: the accumulator's tiles hold different passes (hrt_accum_tile_samples)");
+    *samples = a->ledger.samples(0);
+  });
+}
+
+hrt_status hrt_accum_tile_samples(const hrt_accum* a, uint64_t* per_tile) {
+  return hguard([&] {
+    if (!a || !per_tile) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_tile_samples: null argument"};
+    for (size_t t = 0; t < a->tiles.size(); t++) per_tile[t] = a->ledger.samples(t);
+  });
+}
+
+hrt_status hrt_accum_add_tiles(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, const uint32_t* idx, uint32_t n,
+                               void* stream, hrt_render_stats* stats) {
+  return hguard([&] {
+    if (!a || !cam || !p || !idx || n == 0) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_add_tiles: null argument or no tiles"};
+    accum_add(a, cam, p, idx, n, -1, nullptr, stream, stats);
+  });
+}
+
+hrt_status hrt_accum_noise(hrt_accum* a, float floor, float* d_err, void* stream_, hrt_tile_noise* tiles_out) {
+  return hguard([&] {
+    if (!a || !tiles_out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_noise: null argument"};
+    if (!(floor > 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_noise: floor must be > 0"};
+    accum_usable(a);
+    if (!a->d_m2) throw HipError{HRT_ERR_STATE, "hrt_accum_noise: the accumulator was created without HRT_ACCUM_NOISE"};
+    accum_holds_samples(a);
+    DeviceGuard dg(a->device);
+    hipStream_t stream = (hipStream_t)stream_;
+    const uint32_t nt = (uint32_t)a->tiles.size();
+    upload_noise_tiles(a, stream);
+    hipLaunchKernelGGL(accum_noise, dim3(nt), dim3(accum::NOISE_BLOCK), 0, stream, (const float4*)a->d_acc, (const float*)a->d_m2,
+                       (const NoiseTile*)a->d_ntiles, floor, d_err, a->d_nout);
+    hip_check(hipGetLastError(), "accum_noise launch");
+    std::vector<float2> rec(nt);
+    hip_check(hipMemcpyAsync(rec.data(), a->d_nout, nt * sizeof(float2), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(noise records)");
+    hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize(noise)");
+    for (uint32_t t = 0; t < nt; t++) {
+      tiles_out[t].mean = rec[t].x;
+      tiles_out[t].max = rec[t].y;
+      tiles_out[t].samples = a->ledger.samples(t);
+      tiles_out[t].chunks = a->ledger.chunks(t);
+    }
+  });
+}
+
+hrt_status hrt_debug_accum_moments(hrt_accum* a, float* m2_out) {
+  return hguard([&] {
+    if (!a || !m2_out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_accum_moments: null argument"};
+    if (!a->d_m2) throw HipError{HRT_ERR_STATE, "hrt_debug_accum_moments: the accumulator was created without HRT_ACCUM_NOISE"};
+    DeviceGuard dg(a->device);
+    hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    hip_check(hipMemcpy(m2_out, a->d_m2, a->n_px * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(moments)");
+  });
+}
+
+hrt_status hrt_accum_resolve(hrt_accum* a, int32_t format, void* d_out, void* stream) {
+  return hguard([&] {
+    if (!a || !d_out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_resolve: null argument"};
+    accum_format(format);
+    accum_usable(a);
+    accum_holds_samples(a);
+    DeviceGuard dg(a->device);
+    launch_resolve(a, format, d_out, (hipStream_t)stream);
+  });
+}
+
+hrt_status hrt_accum_resolve_host(hrt_accum* a, int32_t format, void* out) {
+  return hguard([&] {
+    if (!a || !out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_resolve_host: null argument"};
+    accum_format(format);
+    accum_usable(a);
+    accum_holds_samples(a);
+    resolve_to_host(a, format, out, "hipMemcpy(resolve)", [&](void* d_out) { launch_resolve(a, format, d_out, nullptr); });
+  });
+}
+
+hrt_status hrt_accum_resolve_filtered(hrt_accum* a, const hrt_filter_params* f, int32_t format, void* d_out, void* stream) {
+  return hguard([&] {
+    if (!a || !f || !d_out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_resolve_filtered: null argument"};
+    accum_format(format);
+    filter_args(f);
+    filter_state(a);
+    DeviceGuard dg(a->device);
+    launch_filtered(a, f, format, d_out, (hipStream_t)stream);
+  });
+}
+
+hrt_status hrt_accum_resolve_filtered_host(hrt_accum* a, const hrt_filter_params* f, int32_t format, void* out) {
+  return hguard([&] {
+    if (!a || !f || !out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_resolve_filtered_host: null argument"};
+    accum_format(format);
+    filter_args(f);
+    filter_state(a);
+    resolve_to_host(a, format, out, "hipMemcpy(filtered resolve)", [&](void* d_out) { launch_filtered(a, f, format, d_out, nullptr); });
+  });
+}
+
+hrt_status hrt_accum_merge(hrt_accum* dst, const hrt_accum* src, void* stream) {
+  return hguard([&] {
+    if (!dst || !src || dst == src) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_merge: null argument, or an accumulator into itself"};
+    accum_usable(dst);
+    accum_usable(src);
+    if ((dst->d_m2 != nullptr) != (src->d_m2 != nullptr))
+      throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_merge: one accumulator keeps a noise plane (HRT_ACCUM_NOISE), the other none"};
+    accum_uniform(dst, HRT_ERR_UNSUPPORTED, "hrt_accum_merge: the accumulator's tiles hold different passes");
+    accum_uniform(src, HRT_ERR_UNSUPPORTED, "hrt_accum_merge: the accumulator's tiles hold different passes");
+    if (dst->device != src->device || dst->width != src->width || dst->height != src->height ||
+        dst->tiles.size() != src->tiles.size() ||
+        memcmp(dst->tiles.data(), src->tiles.data(), dst->tiles.size() * sizeof(hrt_tile)) != 0)
+      throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_merge: the accumulators differ in device, image size or tiles"};
+    if (src->ledger.empty()) return;
+    check_identity(dst, src->identity);
+    for (const SampleRange& r : *src->ledger.ranges()) check_range(dst->ledger.may_add(r));
+    DeviceGuard dg(dst->device);
+    hipLaunchKernelGGL(accum_merge, dim3(stream_blocks(dst->n_px)), dim3(256), 0, (hipStream_t)stream, dst->d_acc,
+                       (const float4*)src->d_acc, dst->n_px);
+    hip_check(hipGetLastError(), "accum_merge launch");
+    if (dst->d_m2) {
+      hipLaunchKernelGGL(accum_merge_m2, dim3(stream_blocks(dst->n_px)), dim3(256), 0, (hipStream_t)stream, dst->d_m2,
+                         (const float*)src->d_m2, dst->n_px);
+      hip_check(hipGetLastError(), "accum_merge_m2 launch");
+    }
+    dst->ledger.merge(src->ledger);
+    dst->identity = src->identity;
+    dst->has_identity = true;
+  });
+}
+
+hrt_status hrt_accum_download(hrt_accum* a, float* sums, uint32_t* ranges, uint32_t cap, uint32_t* n_ranges) {
+  return hguard([&] {
+    if (!a || !n_ranges) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_download: null argument"};
+    accum_usable(a);
+    accum_uniform(a, HRT_ERR_UNSUPPORTED, "hrt_accum_download: the accumulator's tiles hold different passes");
+    const std::vector<SampleRange>& held = *a->ledger.ranges();
+    *n_ranges = (uint32_t)held.size();
+    if (!sums || cap < held.size()) return;
+    if (!ranges && !held.empty()) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_download: null ranges"};
+    for (size_t i = 0; i < held.size(); i++) {
+      ranges[2 * i] = (uint32_t)held[i].begin;
+      ranges[2 * i + 1] = (uint32_t)held[i].end; /* 2^32 wraps to 0 */
+    }
+    DeviceGuard dg(a->device);
+    hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    hip_check(hipMemcpy(sums, a->d_acc, a->n_px * sizeof(float4), hipMemcpyDeviceToHost), "hipMemcpy(download)");
+  });
+}
+
+hrt_status hrt_accum_upload(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, const float* sums,
+                            const uint32_t* ranges, uint32_t n_ranges) {
+  return hguard([&] {
+    if (!a || !cam || !p || !sums || (!ranges && n_ranges)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_upload: null argument"};
+    accum_usable(a);
+    if (a->d_m2) throw HipError{HRT_ERR_UNSUPPORTED, "hrt_accum_upload: the noise plane of a HRT_ACCUM_NOISE accumulator does not travel"};
+    accum_uniform(a, HRT_ERR_UNSUPPORTED, "hrt_accum_upload: the accumulator's tiles hold different passes");
+    const FrameIdentity id = frame_identity(cam, p);
+    check_identity(a, id);
+    /* the ranges must be addable one after the other: checked on a copy, so an error changes nothing */
+    AccumLedger held = a->ledger;
+    for (uint32_t i = 0; i < n_ranges; i++) {
+      const SampleRange r{ranges[2 * i], ranges[2 * i + 1] == 0 ? (1ull << 32) : ranges[2 * i + 1]};
+      check_range(held.may_add(r));
+      held.record(r, 0);
+    }
+    if (n_ranges == 0) return;
+    DeviceGuard dg(a->device);
+    hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    if (a->ledger.empty()) { /* no samples: the sums as they are */
+      hip_check(hipMemcpy(a->d_acc, sums, a->n_px * sizeof(float4), hipMemcpyHostToDevice), "hipMemcpy(upload)");
+    } else {
+      DevBuf<float4> tmp(a->n_px * sizeof(float4));
+      hip_check(hipMemcpy(tmp.p, sums, a->n_px * sizeof(float4), hipMemcpyHostToDevice), "hipMemcpy(upload)");
+      hipLaunchKernelGGL(accum_merge, dim3(stream_blocks(a->n_px)), dim3(256), 0, nullptr, a->d_acc, (const float4*)tmp.p, a->n_px);
+      hip_check(hipGetLastError(), "accum_merge launch");
+      hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    }
+    a->identity = id;
+    a->has_identity = true;
+    a->ledger = held;
+  });
+}
+
+hrt_status hrt_debug_accumulate(int32_t on_device, const float* partial, uint32_t n_chunks, uint32_t n, float* acc_inout,
+                                uint64_t samples, int32_t format, void* out) {
+  return hguard([&] {
+    if (!partial || !acc_inout || n_chunks == 0 || format < -1 || format > HRT_ACCUM_RGBA8 ||
+        (format >= 0 && (!out || samples == 0 || samples > (1ull << 32))))
+      throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_accumulate: bad argument"};
+    if (n == 0) return;
+    const float scale = format >= 0 ? accum::resolve_scale(samples) : 0.0f;
+    const size_t out_bytes = format < 0 ? 0 : (size_t)n * (format == HRT_ACCUM_F32 ? 16u : 4u);
+    if (!on_device) {
+      const float4* hp = reinterpret_cast<const float4*>(partial);
+      float4* ha = reinterpret_cast<float4*>(acc_inout);
+      with_format<true>(format, [&](auto fc) {
+        for (size_t i = 0; i < n; i++) accumulate_pixel<decltype(fc)::value>(hp, ha, n, n_chunks, scale, out, i);
+      });
+      return;
+    }
+    /* the real kernels on the calling thread's current device: the fused accumulate + resolve, and the separate
+     * resolve of the same sums, which must agree */
+    const size_t p_bytes = (size_t)n_chunks * n * sizeof(float4), a_bytes = (size_t)n * sizeof(float4);
+    DevBuf<float4> d_partial(p_bytes, partial), d_acc(a_bytes, acc_inout);
+    DevBuf<uint8_t> d_out(out_bytes + 16), d_out2(out_bytes + 16);
+    launch_accumulate(format, d_partial.p, d_acc.p, n, n_chunks, scale, d_out.p, nullptr);
+    hip_check(hipMemcpy(acc_inout, d_acc.p, a_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+    if (format < 0) return;
+    resolve_pixels(format, d_acc.p, n, scale, d_out2.p, nullptr);
+    std::vector<uint8_t> second(out_bytes);
+    hip_check(hipMemcpy(out, d_out.p, out_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+    hip_check(hipMemcpy(second.data(), d_out2.p, out_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+    if (memcmp(out, second.data(), out_bytes) != 0)
+      throw HipError{HRT_ERR_STATE, "hrt_debug_accumulate: accumulate_chunks' fused resolve and accum_resolve differ"};
+  });
+}
+
+hrt_status hrt_debug_noise(int32_t on_device, const float* partial, const uint32_t* sizes, uint32_t n_chunks, uint32_t n,
+                           float* acc_inout, float* m2_inout, uint64_t samples, uint64_t chunks, float floor, float* err_out,
+                           float* mean_max_out) {
+  return hguard([&] {
+    if (!partial || !sizes || !acc_inout || !m2_inout || !err_out || !mean_max_out || n_chunks == 0 || n == 0 || samples == 0 ||
+        samples > (1ull << 32))
+      throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_noise: bad argument"};
+    for (uint32_t c = 0; c < n_chunks; c++)
+      if (sizes[c] == 0) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_noise: an empty chunk"};
+    if (!(floor > 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_noise: floor must be > 0"};
+    const NoiseTile T = noise_tile(0, n, samples, chunks);
+    const G::TileDev map{0, 0, n, 1, (n + 7) / 8, 0, 0, 0}; /* one tile: the launch's pixels onto themselves */
+    if (!on_device) {
+      const float4* hp = reinterpret_cast<const float4*>(partial);
+      float4* ha = reinterpret_cast<float4*>(acc_inout);
+      const MomentArgs<true> M{m2_inout, &map, 1u, ChunkCounts{sizes, 0, 0, 0}};
+      for (size_t i = 0; i < n; i++) accumulate_pixel_mapped<-1>(hp, ha, n, n_chunks, 0.0f, nullptr, i, M);
+      for (size_t i = 0; i < n; i++)
+        err_out[i] = accum::noise_err(v3(ha[i].x, ha[i].y, ha[i].z), m2_inout[i], T.inv_n, T.inv_k1, T.few != 0u, floor);
+      accum::tile_reduce(err_out, n, mean_max_out[0], mean_max_out[1]);
+      return;
+    }
+    /* the real kernels on the calling thread's current device */
+    const size_t p_bytes = (size_t)n_chunks * n * sizeof(float4), a_bytes = (size_t)n * sizeof(float4), m_bytes = (size_t)n * sizeof(float);
+    DevBuf<float4> d_partial(p_bytes, partial), d_acc(a_bytes, acc_inout);
+    DevBuf<float> d_m2(m_bytes, m2_inout), d_err(m_bytes);
+    DevBuf<uint32_t> d_sizes(n_chunks * sizeof(uint32_t), sizes);
+    DevBuf<G::TileDev> d_map(sizeof(G::TileDev), &map);
+    DevBuf<NoiseTile> d_tile(sizeof(NoiseTile), &T);
+    DevBuf<float2> d_rec(sizeof(float2));
+    const MomentArgs<true> M{d_m2.p, d_map.p, 1u, ChunkCounts{d_sizes.p, 0, 0, 0}};
+    accumulate(-1, d_partial.p, d_acc.p, n, n_chunks, 0.0f, nullptr, M, nullptr);
+    hipLaunchKernelGGL(accum_noise, dim3(1), dim3(accum::NOISE_BLOCK), 0, nullptr, (const float4*)d_acc.p, (const float*)d_m2.p,
+                       (const NoiseTile*)d_tile.p, floor, d_err.p, d_rec.p);
+    hip_check(hipGetLastError(), "accum_noise launch");
+    hip_check(hipMemcpy(acc_inout, d_acc.p, a_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+    hip_check(hipMemcpy(m2_inout, d_m2.p, m_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+    hip_check(hipMemcpy(err_out, d_err.p, m_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+    hip_check(hipMemcpy(mean_max_out, d_rec.p, sizeof(float2), hipMemcpyDeviceToHost), "hipMemcpy");
+  });
+}
+
+hrt_status hrt_debug_filter(int32_t on_device, const float* raster, uint32_t width, uint32_t height, uint32_t iterations,
+                            float sigma, float* out) {
+  return hguard([&] {
+    if (!raster || !out || width == 0 || height == 0 || width > 65535 || height > 65535)
+      throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_filter: null argument, or a width or height outside [1, 65535]"};
+    const hrt_filter_params f{iterations, sigma};
+    filter_args(&f);
+    if (!on_device) return filter::filter_raster(raster, width, height, iterations, sigma, out);
+    /* the real kernels on the calling thread's current device: one tile that covers the raster, so the packed
+     * order of the last iteration's output is the raster's */
+    const size_t bytes = (size_t)width * height * sizeof(float4);
+    const filter::FilterTile T{0, 0, width, height, 0, 0, 0.0f, 0.0f};
+    DevBuf<float4> d_a(bytes, raster), d_b(bytes), d_out(bytes);
+    DevBuf<filter::FilterTile> d_tile(sizeof(filter::FilterTile), &T);
+    filter::launch_atrous(d_a.p, d_b.p, width, height, d_tile.p, 1, filter::tile_blocks(width, height), iterations, sigma,
+                          filter::FORMAT_RAW, d_out.p, nullptr);
+    hip_check(hipMemcpy(out, d_out.p, bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+  });
+}
+
+}  // extern "C"

@@ -128,7 +128,7 @@ inline void filter_raster(const float* in, uint32_t width, uint32_t height, uint
   for (size_t k = 0; k < 4 * n; k++) out[k] = a[k];
 }
 
-/* ---- the launches of filter.hip, for the accumulator code in render.hip (streams are hipStream_t) ---- */
+/* ---- the launches of filter.hip, for the accumulator code in accum.hip (streams are hipStream_t) ---- */
 
 /* One tile as filter_gather and the last filter_atrous see it.  The tile-block domain: a tile is cut into
  * BLOCK_W x BLOCK_H pixel blocks, row-major, and the tiles' blocks are numbered in tile order starting at blk0. */
