@@ -1,7 +1,8 @@
 /*
  * accum.hip — the sample accumulator (hrt_accum, include/hrt/hrt.h): its streaming kernels (arithmetic: accum.h), host
  * state and entry points.  A pass is render.hip's render_launch, which ends in launch_accumulate{,_mapped} below; the
- * samples and chunks each tile then holds are accum_ledger.h's book; the filtered resolve's kernels are filter.hip's.
+ * samples and chunks each tile then holds are accum_ledger.h's book; the filtered resolve's kernels are filter.hip's,
+ * the feature pass's feature_pass.hip's and the guided resolve's guided.hip's.
  */
 #include <hip/hip_runtime.h>
 
@@ -11,7 +12,9 @@
 
 #include "accum.h"
 #include "accum_ledger.h"
+#include "feature_pass.h"
 #include "filter.h"
+#include "guided.h"
 #include "render_host.h"
 
 using namespace hrt;
@@ -273,6 +276,15 @@ struct hrt_accum {
   float4* d_fplane[2] = {nullptr, nullptr};
   filter::FilterTile* d_ftiles = nullptr;
   std::vector<filter::FilterTile> h_ftiles;
+  /* HRT_ACCUM_FEATURES: the two planes of first-hit feature sums (feature_pass.h: fa = (albedo.xyz, hit), fn = (normal.xyz,
+   * depth)), packed as d_acc, the feature samples held (a ledger of its own: every feature pass covers every tile) and
+   * the tiles as feature_kernel sees them */
+  float4 *d_fa = nullptr, *d_fn = nullptr;
+  AccumLedger f_ledger;
+  features::FeatureTile* d_feat_tiles = nullptr;
+  uint32_t feat_blocks = 0, feat_log_bw = 0;
+  /* the guided resolve's two mean feature rasters over the planes' bounding box, made by the first guided resolve */
+  float4* d_gplane[2] = {nullptr, nullptr};
 };
 
 namespace {
@@ -405,7 +417,8 @@ void filter_prepare(hrt_accum* a, hipStream_t stream) {
   a->f_w = w, a->f_h = h, a->f_blocks = (uint32_t)blocks;
   a->f_state = 1;
 }
-void launch_filtered(hrt_accum* a, const hrt_filter_params* f, int32_t format, void* d_out, hipStream_t stream) {
+/* the sums and m2 gathered onto plane 0 */
+void filter_gather_plane(hrt_accum* a, hipStream_t stream) {
   filter_prepare(a, stream);
   upload_noise_tiles(a, stream); /* each tile's own 1 / N and 1 / (K - 1) */
   const uint32_t nt = (uint32_t)a->tiles.size();
@@ -416,8 +429,50 @@ void launch_filtered(hrt_accum* a, const hrt_filter_params* f, int32_t format, v
   hip_check(hipMemcpyAsync(a->d_ftiles, a->h_ftiles.data(), nt * sizeof(filter::FilterTile), hipMemcpyHostToDevice, stream),
             "hipMemcpyAsync(filter tiles)");
   filter::launch_gather(a->d_acc, a->d_m2, a->d_ftiles, nt, a->f_blocks, a->d_fplane[0], a->f_w, stream);
-  filter::launch_atrous(a->d_fplane[0], a->d_fplane[1], a->f_w, a->f_h, a->d_ftiles, nt, a->f_blocks, f->iterations, f->sigma,
-                        format, d_out, stream);
+}
+void launch_filtered(hrt_accum* a, const hrt_filter_params* f, int32_t format, void* d_out, hipStream_t stream) {
+  filter_gather_plane(a, stream);
+  filter::launch_atrous(a->d_fplane[0], a->d_fplane[1], a->f_w, a->f_h, a->d_ftiles, (uint32_t)a->tiles.size(), a->f_blocks,
+                        f->iterations, f->sigma, format, d_out, stream);
+}
+
+/* hrt_accum_resolve_guided's checks beyond the filtered resolve's, and its tolerances as guided.h takes them */
+float guided_term(float tolerance) {
+  if (!(tolerance >= 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_guided_params: a tolerance is negative or NaN"};
+  return tolerance > 0.0f ? 1.0f / tolerance : 0.0f;
+}
+guided::Terms guided_args(const hrt_guided_params* g) {
+  const hrt_filter_params f{g->iterations, g->sigma};
+  filter_args(&f);
+  return guided::Terms{guided_term(g->normal), guided_term(g->albedo), guided_term(g->depth)};
+}
+void features_flag(const hrt_accum* a, const char* who) {
+  if (!a->d_fa) throw HipError{HRT_ERR_STATE, std::string(who) + ": the accumulator was created without HRT_ACCUM_FEATURES"};
+}
+uint64_t feature_samples(const hrt_accum* a) { return a->f_ledger.samples(0); }
+void guided_state(const hrt_accum* a) {
+  accum_usable(a);
+  features_flag(a, "hrt_accum_resolve_guided");
+  filter_state(a);
+  if (feature_samples(a) == 0) throw HipError{HRT_ERR_STATE, "hrt_accum_resolve_guided: the accumulator holds no feature samples"};
+}
+void launch_guided(hrt_accum* a, const hrt_guided_params* g, const guided::Terms& K, int32_t format, void* d_out, hipStream_t stream) {
+  filter_gather_plane(a, stream);
+  if (!a->d_gplane[0]) { /* the two feature rasters, once: a present pixel's features are written by every resolve */
+    float4* plane[2] = {nullptr, nullptr};
+    try {
+      for (float4*& pl : plane) hip_check(hipMalloc((void**)&pl, (size_t)a->f_w * a->f_h * sizeof(float4)), "hipMalloc(feature raster)");
+    } catch (...) {
+      if (plane[0]) (void)hipFree(plane[0]);
+      throw;
+    }
+    a->d_gplane[0] = plane[0], a->d_gplane[1] = plane[1];
+  }
+  const uint32_t nt = (uint32_t)a->tiles.size();
+  guided::launch_gather_features(a->d_fa, a->d_fn, a->d_ftiles, nt, a->f_blocks, 1.0f / (float)feature_samples(a), a->d_gplane[0],
+                                 a->d_gplane[1], a->f_w, stream);
+  guided::launch_guided(a->d_fplane[0], a->d_fplane[1], a->d_gplane[0], a->d_gplane[1], a->f_w, a->f_h, a->d_ftiles, nt, a->f_blocks,
+                        g->iterations, g->sigma, K, format, d_out, stream);
 }
 
 /* hrt_accum_resolve_host / _filtered_host after their checks: `launch` resolves into a buffer of the scene's pool on
@@ -500,7 +555,7 @@ hrt_status hrt_accum_create_ex(hrt_scene* s, uint32_t width, uint32_t height, co
   return hguard([&] {
     if (!s || !tiles || !out || n_tiles == 0) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_create: null argument or no tiles"};
     *out = nullptr;
-    if (flags & ~(uint32_t)HRT_ACCUM_NOISE) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_create_ex: unknown flag"};
+    if (flags & ~(uint32_t)(HRT_ACCUM_NOISE | HRT_ACCUM_FEATURES)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_create_ex: unknown flag"};
     if (width < 2 || height < 2 || width > 65535 || height > 65535)
       throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_create: 2 <= width, height <= 65535"};
     uint64_t n_px = 0;
@@ -535,6 +590,25 @@ hrt_status hrt_accum_create_ex(hrt_scene* s, uint32_t width, uint32_t height, co
         hip_check(hipMemset(a->d_m2, 0, a->n_px * sizeof(float)), "hipMemset(noise plane)");
         hip_check(hipMalloc((void**)&a->d_nout, n_tiles * sizeof(float2)), "hipMalloc(noise records)");
       }
+      if (flags & HRT_ACCUM_FEATURES) {
+        a->f_ledger = AccumLedger(n_tiles);
+        a->feat_log_bw = features::block_log_w();
+        std::vector<features::FeatureTile> ft(n_tiles);
+        uint64_t blocks = 0;
+        for (uint32_t i = 0; i < n_tiles; i++) {
+          ft[i] = features::FeatureTile{tiles[i].x, tiles[i].y, tiles[i].w, tiles[i].h, a->tile_off[i], (uint32_t)blocks, {0u, 0u}};
+          blocks += features::tile_blocks(tiles[i].w, tiles[i].h, a->feat_log_bw);
+        }
+        if (blocks >= (1ull << 31)) throw HipError{HRT_ERR_UNSUPPORTED, "HRT_ACCUM_FEATURES: too many tile blocks for one launch"};
+        a->feat_blocks = (uint32_t)blocks;
+        for (float4** pl : {&a->d_fa, &a->d_fn}) {
+          hip_check(hipMalloc((void**)pl, a->n_px * sizeof(float4)), "hipMalloc(feature plane)");
+          hip_check(hipMemset(*pl, 0, a->n_px * sizeof(float4)), "hipMemset(feature plane)");
+        }
+        hip_check(hipMalloc((void**)&a->d_feat_tiles, n_tiles * sizeof(features::FeatureTile)), "hipMalloc(feature tiles)");
+        hip_check(hipMemcpy(a->d_feat_tiles, ft.data(), n_tiles * sizeof(features::FeatureTile), hipMemcpyHostToDevice),
+                  "hipMemcpy(feature tiles)");
+      }
     } catch (...) {
       hrt_accum_destroy(a);
       throw;
@@ -555,6 +629,8 @@ void hrt_accum_destroy(hrt_accum* a) {
   for (float4* plane : a->d_fplane)
     if (plane) (void)hipFree(plane);
   if (a->d_ftiles) (void)hipFree(a->d_ftiles);
+  for (void* p : {(void*)a->d_fa, (void*)a->d_fn, (void*)a->d_feat_tiles, (void*)a->d_gplane[0], (void*)a->d_gplane[1]})
+    if (p) (void)hipFree(p);
   if (prev >= 0) (void)hipSetDevice(prev);
   delete a;
 }
@@ -565,7 +641,10 @@ hrt_status hrt_accum_reset(hrt_accum* a, void* stream) {
     DeviceGuard dg(a->device);
     hip_check(hipMemsetAsync(a->d_acc, 0, a->n_px * sizeof(float4), (hipStream_t)stream), "hipMemsetAsync(accumulator)");
     if (a->d_m2) hip_check(hipMemsetAsync(a->d_m2, 0, a->n_px * sizeof(float), (hipStream_t)stream), "hipMemsetAsync(noise plane)");
+    for (float4* pl : {a->d_fa, a->d_fn})
+      if (pl) hip_check(hipMemsetAsync(pl, 0, a->n_px * sizeof(float4), (hipStream_t)stream), "hipMemsetAsync(feature plane)");
     a->ledger.clear();
+    a->f_ledger.clear();
     a->has_identity = false;
     a->invalid = false;
   });
@@ -689,6 +768,93 @@ hrt_status hrt_accum_resolve_filtered_host(hrt_accum* a, const hrt_filter_params
   });
 }
 
+hrt_status hrt_accum_add_features(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, void* stream) {
+  return hguard([&] {
+    if (!a || !cam || !p) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_add_features: null argument"};
+    accum_usable(a);
+    features_flag(a, "hrt_accum_add_features");
+    const FrameIdentity id = frame_identity(cam, p);
+    check_identity(a, id);
+    check_range(a->f_ledger.may_add(SampleRange{p->sample_offset, (uint64_t)p->sample_offset + p->samples}));
+    DeviceGuard dg(a->device);
+    int cull = 0;
+    bool full = false;
+    const KParams kp = feature_params(a->scene, cam, p, cull, full);
+    features::launch_features(cull, full, kp, a->d_feat_tiles, (uint32_t)a->tiles.size(), a->feat_blocks, a->feat_log_bw, a->d_fa,
+                              a->d_fn, stream);
+    a->identity = id;
+    a->has_identity = true;
+    a->f_ledger.record(SampleRange{p->sample_offset, (uint64_t)p->sample_offset + p->samples}, 0);
+  });
+}
+
+hrt_status hrt_accum_feature_samples(const hrt_accum* a, uint64_t* samples) {
+  return hguard([&] {
+    if (!a || !samples) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_feature_samples: null argument"};
+    features_flag(a, "hrt_accum_feature_samples");
+    *samples = feature_samples(a);
+  });
+}
+
+hrt_status hrt_accum_features(hrt_accum* a, void* d_albedo, void* d_normal, void* stream) {
+  return hguard([&] {
+    if (!a || (!d_albedo && !d_normal)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_features: null argument"};
+    accum_usable(a);
+    features_flag(a, "hrt_accum_features");
+    if (feature_samples(a) == 0) throw HipError{HRT_ERR_STATE, "hrt_accum_features: the accumulator holds no feature samples"};
+    DeviceGuard dg(a->device);
+    features::launch_feature_means(a->d_fa, a->d_fn, a->n_px, 1.0f / (float)feature_samples(a), d_albedo, d_normal, stream);
+  });
+}
+
+hrt_status hrt_accum_features_host(hrt_accum* a, float* albedo, float* normal) {
+  return hguard([&] {
+    if (!a || (!albedo && !normal)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_features_host: null argument"};
+    accum_usable(a);
+    features_flag(a, "hrt_accum_features_host");
+    if (feature_samples(a) == 0) throw HipError{HRT_ERR_STATE, "hrt_accum_features_host: the accumulator holds no feature samples"};
+    DeviceGuard dg(a->device);
+    const size_t bytes = a->n_px * sizeof(float4);
+    DevBuf<float4> d_al(bytes), d_no(bytes);
+    hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    features::launch_feature_means(a->d_fa, a->d_fn, a->n_px, 1.0f / (float)feature_samples(a), d_al.p, d_no.p, nullptr);
+    if (albedo) hip_check(hipMemcpy(albedo, d_al.p, bytes, hipMemcpyDeviceToHost), "hipMemcpy(albedo plane)");
+    if (normal) hip_check(hipMemcpy(normal, d_no.p, bytes, hipMemcpyDeviceToHost), "hipMemcpy(normal plane)");
+  });
+}
+
+hrt_status hrt_debug_accum_features(hrt_accum* a, float* fa_out, float* fn_out) {
+  return hguard([&] {
+    if (!a || !fa_out || !fn_out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_accum_features: null argument"};
+    features_flag(a, "hrt_debug_accum_features");
+    DeviceGuard dg(a->device);
+    hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    hip_check(hipMemcpy(fa_out, a->d_fa, a->n_px * sizeof(float4), hipMemcpyDeviceToHost), "hipMemcpy(feature sums)");
+    hip_check(hipMemcpy(fn_out, a->d_fn, a->n_px * sizeof(float4), hipMemcpyDeviceToHost), "hipMemcpy(feature sums)");
+  });
+}
+
+hrt_status hrt_accum_resolve_guided(hrt_accum* a, const hrt_guided_params* g, int32_t format, void* d_out, void* stream) {
+  return hguard([&] {
+    if (!a || !g || !d_out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_resolve_guided: null argument"};
+    accum_format(format);
+    const guided::Terms K = guided_args(g);
+    guided_state(a);
+    DeviceGuard dg(a->device);
+    launch_guided(a, g, K, format, d_out, (hipStream_t)stream);
+  });
+}
+
+hrt_status hrt_accum_resolve_guided_host(hrt_accum* a, const hrt_guided_params* g, int32_t format, void* out) {
+  return hguard([&] {
+    if (!a || !g || !out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_resolve_guided_host: null argument"};
+    accum_format(format);
+    const guided::Terms K = guided_args(g);
+    guided_state(a);
+    resolve_to_host(a, format, out, "hipMemcpy(guided resolve)", [&](void* d_out) { launch_guided(a, g, K, format, d_out, nullptr); });
+  });
+}
+
 hrt_status hrt_accum_merge(hrt_accum* dst, const hrt_accum* src, void* stream) {
   return hguard([&] {
     if (!dst || !src || dst == src) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_merge: null argument, or an accumulator into itself"};
@@ -702,10 +868,23 @@ hrt_status hrt_accum_merge(hrt_accum* dst, const hrt_accum* src, void* stream) {
         dst->tiles.size() != src->tiles.size() ||
         memcmp(dst->tiles.data(), src->tiles.data(), dst->tiles.size() * sizeof(hrt_tile)) != 0)
       throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_merge: the accumulators differ in device, image size or tiles"};
-    if (src->ledger.empty()) return;
+    if ((dst->d_fa != nullptr) != (src->d_fa != nullptr))
+      throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_merge: one accumulator keeps feature planes (HRT_ACCUM_FEATURES), the other none"};
+    const bool feats = src->d_fa && !src->f_ledger.empty();
+    if (src->ledger.empty() && !feats) return;
     check_identity(dst, src->identity);
-    for (const SampleRange& r : *src->ledger.ranges()) check_range(dst->ledger.may_add(r));
+    if (!src->ledger.empty())
+      for (const SampleRange& r : *src->ledger.ranges()) check_range(dst->ledger.may_add(r));
+    if (feats)
+      for (const SampleRange& r : *src->f_ledger.ranges()) check_range(dst->f_ledger.may_add(r));
     DeviceGuard dg(dst->device);
+    if (feats) {
+      features::launch_feature_merge(dst->d_fa, dst->d_fn, src->d_fa, src->d_fn, dst->n_px, stream);
+      dst->f_ledger.merge(src->f_ledger);
+      dst->identity = src->identity;
+      dst->has_identity = true;
+    }
+    if (src->ledger.empty()) return;
     hipLaunchKernelGGL(accum_merge, dim3(stream_blocks(dst->n_px)), dim3(256), 0, (hipStream_t)stream, dst->d_acc,
                        (const float4*)src->d_acc, dst->n_px);
     hip_check(hipGetLastError(), "accum_merge launch");
@@ -865,6 +1044,27 @@ hrt_status hrt_debug_filter(int32_t on_device, const float* raster, uint32_t wid
     DevBuf<filter::FilterTile> d_tile(sizeof(filter::FilterTile), &T);
     filter::launch_atrous(d_a.p, d_b.p, width, height, d_tile.p, 1, filter::tile_blocks(width, height), iterations, sigma,
                           filter::FORMAT_RAW, d_out.p, nullptr);
+    hip_check(hipMemcpy(out, d_out.p, bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+  });
+}
+
+hrt_status hrt_debug_guided(int32_t on_device, const float* raster, const float* albedo, const float* normal, uint32_t width,
+                            uint32_t height, uint32_t iterations, float sigma, float kn, float ka, float kz, float* out) {
+  return hguard([&] {
+    if (!raster || !albedo || !normal || !out || width == 0 || height == 0 || width > 65535 || height > 65535)
+      throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_guided: null argument, or a width or height outside [1, 65535]"};
+    const hrt_filter_params f{iterations, sigma};
+    filter_args(&f);
+    if (!(kn >= 0.0f) || !(ka >= 0.0f) || !(kz >= 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_guided: a negative or NaN term"};
+    const guided::Terms K{kn, ka, kz};
+    if (!on_device) return guided::guided_raster(raster, albedo, normal, width, height, iterations, sigma, K, out);
+    /* the real kernels on the calling thread's current device, over one tile that covers the raster (hrt_debug_filter) */
+    const size_t bytes = (size_t)width * height * sizeof(float4);
+    const filter::FilterTile T{0, 0, width, height, 0, 0, 0.0f, 0.0f};
+    DevBuf<float4> d_a(bytes, raster), d_b(bytes), d_al(bytes, albedo), d_no(bytes, normal), d_out(bytes);
+    DevBuf<filter::FilterTile> d_tile(sizeof(filter::FilterTile), &T);
+    guided::launch_guided(d_a.p, d_b.p, d_al.p, d_no.p, width, height, d_tile.p, 1, filter::tile_blocks(width, height), iterations, sigma,
+                          K, filter::FORMAT_RAW, d_out.p, nullptr);
     hip_check(hipMemcpy(out, d_out.p, bytes, hipMemcpyDeviceToHost), "hipMemcpy");
   });
 }

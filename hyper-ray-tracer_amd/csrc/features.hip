@@ -1,0 +1,115 @@
+/*
+ * features.hip — the kernels of the first-hit feature pass (hrt_accum_add_features; per-lane code: feature_pass.h).
+ *
+ *   feature_kernel   one lane per pixel, one wave per workgroup.  A wave covers one block of the tile-block domain
+ *                    (feature_pass.h FeatureTile): a compact bw x bh pixel block, so its 64 camera rays stay coherent in the
+ *                    walk.  The lane runs the pass's samples in index order, sums them in registers and adds the pass
+ *                    sum to its pixel of the two packed planes.  The scene is read from global memory.
+ *   feature_means    (fa, fn) -> the mean planes.
+ *   feature_merge    dst += src.
+ */
+#include <hip/hip_runtime.h>
+
+#include <cstdlib>
+
+#include "feature_pass.h"
+#include "kernel_common.h"
+#include "render_host.h"
+
+using namespace hrt;
+using namespace hrt::features;
+
+namespace {
+
+/* block b of the tile-block domain -> its tile: the last one whose blk0 <= b */
+__device__ inline FeatureTile tile_of_block(const FeatureTile* __restrict__ tiles, uint32_t n_tiles, uint32_t b) {
+  uint32_t lo = 0, hi = n_tiles;
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (tiles[mid].blk0 <= b) lo = mid;
+    else hi = mid;
+  }
+  return tiles[lo];
+}
+
+template <int CULL, bool FULL>
+__global__ __launch_bounds__(64) void feature_kernel(KParams P, const FeatureTile* __restrict__ tiles, uint32_t n_tiles, uint32_t log_bw,
+                                                     float4* __restrict__ fa, float4* __restrict__ fn) {
+  const FeatureTile T = tile_of_block(tiles, n_tiles, blockIdx.x);
+  const uint32_t bw = 1u << log_bw, bh = 64u >> log_bw;
+  const uint32_t nbx = (T.w + bw - 1) / bw, k = blockIdx.x - T.blk0;
+  const uint32_t lx = (k % nbx) * bw + (threadIdx.x & (bw - 1)), ly = (k / nbx) * bh + (threadIdx.x >> log_bw);
+  if (lx >= T.w || ly >= T.h) return;
+  const Sums s = pass_sums<CULL, FULL>(P, P.nodes, P.prims, T.x + lx, T.y + ly, P.spp);
+  const size_t i = (size_t)T.off + (size_t)ly * T.w + lx;
+  Sums plane;
+  plane.fa = fa[i];
+  plane.fn = fn[i];
+  plane = add_pass(plane, s);
+  fa[i] = plane.fa;
+  fn[i] = plane.fn;
+}
+
+__global__ __launch_bounds__(256) void feature_means(const float4* __restrict__ fa, const float4* __restrict__ fn, size_t n, float inv,
+                                                     float4* __restrict__ albedo, float4* __restrict__ normal) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const float4 a = fa[i];
+    if (albedo) albedo[i] = mean_albedo(a, inv);
+    if (normal) normal[i] = mean_normal(a, fn[i], inv);
+  }
+}
+
+__global__ __launch_bounds__(256) void feature_merge(float4* __restrict__ fa, float4* __restrict__ fn, const float4* __restrict__ s_fa,
+                                                     const float4* __restrict__ s_fn, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    fa[i] = add4(fa[i], s_fa[i]);
+    fn[i] = add4(fn[i], s_fn[i]);
+  }
+}
+
+template <int CULL, bool FULL>
+void launch_one(const KParams& P, const FeatureTile* tiles, uint32_t n_tiles, uint32_t blocks, uint32_t log_bw, float4* fa, float4* fn,
+                hipStream_t stream) {
+  hipLaunchKernelGGL((feature_kernel<CULL, FULL>), dim3(blocks), dim3(64), 0, stream, P, tiles, n_tiles, log_bw, fa, fn);
+  hip_check(hipGetLastError(), "feature_kernel launch");
+}
+
+}  // namespace
+
+namespace hrt {
+namespace features {
+
+uint32_t block_log_w() {
+  const char* v = knob_env("HRT_FEATURE_BLOCK_W");
+  const long w = v ? strtol(v, nullptr, 10) : 8;
+  for (uint32_t l = 0; l <= 6; l++)
+    if (w == (1l << l)) return l;
+  return 3;
+}
+
+void launch_features(int cull, bool full, const KParams& P, const FeatureTile* d_tiles, uint32_t n_tiles, uint32_t n_blocks,
+                     uint32_t log_bw, void* d_fa, void* d_fn, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  float4 *fa = (float4*)d_fa, *fn = (float4*)d_fn;
+  namespace G = hrt::gpu;
+  if (full && cull == G::CULL_EXACT) launch_one<G::CULL_EXACT, true>(P, d_tiles, n_tiles, n_blocks, log_bw, fa, fn, stream);
+  else if (cull == G::CULL_EXACT) launch_one<G::CULL_EXACT, false>(P, d_tiles, n_tiles, n_blocks, log_bw, fa, fn, stream);
+  else if (cull != G::CULL_REFERENCE) throw HipError{HRT_ERR_UNSUPPORTED, "feature pass: an approximate culling mode"};
+  else if (full) launch_one<G::CULL_REFERENCE, true>(P, d_tiles, n_tiles, n_blocks, log_bw, fa, fn, stream);
+  else launch_one<G::CULL_REFERENCE, false>(P, d_tiles, n_tiles, n_blocks, log_bw, fa, fn, stream);
+}
+
+void launch_feature_means(const void* d_fa, const void* d_fn, size_t n, float inv, void* d_albedo, void* d_normal, void* stream) {
+  hipLaunchKernelGGL(feature_means, dim3(stream_blocks(n)), dim3(256), 0, (hipStream_t)stream, (const float4*)d_fa, (const float4*)d_fn, n,
+                     inv, (float4*)d_albedo, (float4*)d_normal);
+  hip_check(hipGetLastError(), "feature_means launch");
+}
+
+void launch_feature_merge(void* d_fa, void* d_fn, const void* s_fa, const void* s_fn, size_t n, void* stream) {
+  hipLaunchKernelGGL(feature_merge, dim3(stream_blocks(n)), dim3(256), 0, (hipStream_t)stream, (float4*)d_fa, (float4*)d_fn,
+                     (const float4*)s_fa, (const float4*)s_fn, n);
+  hip_check(hipGetLastError(), "feature_merge launch");
+}
+
+}  // namespace features
+}  // namespace hrt

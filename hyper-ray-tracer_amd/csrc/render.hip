@@ -856,6 +856,22 @@ void hrt::chunk_schedule(const hrt_scene* s, const hrt_render_params* p, uint32_
                s->opts.chunk_max, s->opts.chunk_uniform ? 0u : 32u, chunk, n_head, first, n_tail);
 }
 
+/* The kernel parameters of a feature pass (features.hip reads the scene from global memory: nothing is staged) and
+ * the instantiation the plan names, as hrt_debug_trace_path picks its own.  Approximate plans are refused. */
+KParams hrt::feature_params(hrt_scene* s, const hrt_camera* cam, const hrt_render_params* p, int& cull, bool& full) {
+  if (!s->committed || !s->d_blob) throw HipError{HRT_ERR_STATE, "scene not committed"};
+  check_render_args(cam, p);
+  const Plan pl = plan(s, cam, p->flags);
+  if ((p->flags & (HRT_RENDER_FAST_CULL | HRT_RENDER_SAH)) != 0 || pl.fast || pl.cull == G::CULL_SLAB)
+    throw HipError{HRT_ERR_UNSUPPORTED, "hrt_accum_add_features: an approximate plan (HRT_RENDER_FAST_CULL / HRT_RENDER_SAH)"};
+  cull = pl.cull;
+  full = pl.full || pl.heavy;
+  Plan global = pl; /* the reference stream in global memory, the Perlin tables too */
+  global.fast = false;
+  global.perlin_lds = false;
+  return scene_params(s, cam, p, global);
+}
+
 /* One render launch of a tile set, shared by every entry point up to where its sums go (dst): argument checks, the
  * chunk schedule, tile table and stride, the scratch slot, plan, claim set-up, the megakernel, then reduce_chunks
  * (a frame) or accumulate_chunks (an accumulator), the stats copy-back and the slot's error word.  *launched is

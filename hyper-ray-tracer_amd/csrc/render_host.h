@@ -83,6 +83,9 @@ struct SumsDest {
 /* render.hip: one render launch of a tile set, up to where its sums go (dst) */
 void render_launch(hrt_scene* s, const hrt_camera* cam, const hrt_render_params* p, const hrt_tile* tiles, uint32_t n_tiles,
                    const SumsDest& dst, void* stream, hrt_render_stats* stats, bool* launched);
+/* render.hip: the kernel parameters of a feature pass over samples [p->sample_offset, + p->samples) and the
+ * instantiation its plan names (cull: layout.h CULL_EXACT or CULL_REFERENCE); an approximate plan is HRT_ERR_UNSUPPORTED */
+lane::KParams feature_params(hrt_scene* s, const hrt_camera* cam, const hrt_render_params* p, int& cull, bool& full);
 /* render.hip: a render's sample chunks (lane.h frame_chunks) */
 void chunk_schedule(const hrt_scene* s, const hrt_render_params* p, uint32_t& chunk, uint32_t& n_head, uint32_t& first,
                     uint32_t& n_tail);

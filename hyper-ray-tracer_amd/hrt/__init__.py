@@ -153,6 +153,13 @@ class FilterParams(ctypes.Structure):
     _fields_ = [("iterations", ctypes.c_uint32), ("sigma", ctypes.c_float)]
 
 
+class GuidedParams(ctypes.Structure):
+    """hrt_guided_params: the a-trous filter's iterations and sigma, and the tolerances of the normal, albedo and depth
+    terms (0: the term is off)."""
+    _fields_ = [("iterations", ctypes.c_uint32), ("sigma", ctypes.c_float), ("normal", ctypes.c_float),
+                ("albedo", ctypes.c_float), ("depth", ctypes.c_float)]
+
+
 class SceneOptions(ctypes.Structure):
     """hrt_scene_options: the explicit configuration that can change an image's bits (all-zero = default)."""
     _fields_ = [(n, ctypes.c_uint32) for n in ("bvh_ties", "walk_tree", "chunk_min", "chunk_max", "chunk_uniform")]
@@ -166,7 +173,9 @@ OPTIONAL = {"hrt_abi_version", "hrt_last_launch", "hrt_debug_box_test", "hrt_sce
             "hrt_accum_upload", "hrt_debug_accumulate", "hrt_debug_walk_regroup",
             "hrt_accum_create_ex", "hrt_accum_add_tiles", "hrt_accum_noise", "hrt_accum_tile_samples", "hrt_debug_noise",
             "hrt_debug_accum_moments",
-            "hrt_accum_resolve_filtered", "hrt_accum_resolve_filtered_host", "hrt_debug_filter"}
+            "hrt_accum_resolve_filtered", "hrt_accum_resolve_filtered_host", "hrt_debug_filter",
+        "hrt_accum_add_features", "hrt_accum_feature_samples", "hrt_accum_features", "hrt_accum_features_host",
+            "hrt_accum_resolve_guided", "hrt_accum_resolve_guided_host", "hrt_debug_guided", "hrt_debug_accum_features"}
 HRT_LIB_OVERRIDE = bool(os.environ.get("HRT_LIB"))
 
 # Every entry point of include/hrt/hrt.h (tests/test_abi.py checks the header against this list).
@@ -187,6 +196,8 @@ EXPORTS = [
     "hrt_accum_create_ex", "hrt_accum_add_tiles", "hrt_accum_noise", "hrt_accum_tile_samples", "hrt_debug_noise",
     "hrt_debug_accum_moments",
     "hrt_accum_resolve_filtered", "hrt_accum_resolve_filtered_host", "hrt_debug_filter",
+    "hrt_accum_add_features", "hrt_accum_feature_samples", "hrt_accum_features", "hrt_accum_features_host",
+    "hrt_accum_resolve_guided", "hrt_accum_resolve_guided_host", "hrt_debug_guided", "hrt_debug_accum_features",
 ]
 
 ABI_VERSION = 6  # include/hrt/hrt.h HRT_ABI_VERSION: the struct layouts below
@@ -289,6 +300,14 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "hrt_accum_resolve_filtered": (S, [vp, ctypes.POINTER(FilterParams), i32, vp, vp]),
         "hrt_accum_resolve_filtered_host": (S, [vp, ctypes.POINTER(FilterParams), i32, vp]),
         "hrt_debug_filter": (S, [i32, vp, u32, u32, u32, f, vp]),
+        "hrt_accum_add_features": (S, [vp, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams), vp]),
+        "hrt_accum_feature_samples": (S, [vp, ctypes.POINTER(u64)]),
+        "hrt_accum_features": (S, [vp, vp, vp, vp]),
+        "hrt_accum_features_host": (S, [vp, vp, vp]),
+        "hrt_accum_resolve_guided": (S, [vp, ctypes.POINTER(GuidedParams), i32, vp, vp]),
+        "hrt_accum_resolve_guided_host": (S, [vp, ctypes.POINTER(GuidedParams), i32, vp]),
+        "hrt_debug_guided": (S, [i32, vp, vp, vp, u32, u32, u32, f, f, f, f, vp]),
+        "hrt_debug_accum_features": (S, [vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         if name in OPTIONAL and HRT_LIB_OVERRIDE and not hasattr(L, name):
@@ -562,7 +581,7 @@ def render_tiles_device(scene: Scene, cam: Camera, p: RenderParams, tiles, d_out
 
 
 ACCUM_F32, ACCUM_RGBA8 = 0, 1
-ACCUM_NOISE = 1  # hrt_accum_create_ex flag
+ACCUM_NOISE, ACCUM_FEATURES = 1, 4  # hrt_accum_create_ex flags
 _ACCUM_FORMATS = {"f32": ACCUM_F32, "rgba8": ACCUM_RGBA8}
 
 
@@ -571,22 +590,36 @@ def filter_params(iterations: int = 3, sigma: float = 4.0) -> FilterParams:
     return FilterParams(int(iterations), float(sigma))
 
 
+# the guided filter's default tolerances (the sweep over both test inputs; a normal term this
+# tight is what keeps geometry smaller than the footprint)
+GUIDED_DEFAULTS = dict(normal=0.1, albedo=0.1, depth=0.1)
+
+
+def guided_params(iterations: int = 3, sigma: float = 4.0, normal: Optional[float] = None, albedo: Optional[float] = None,
+                  depth: Optional[float] = None) -> GuidedParams:
+    """hrt_guided_params with the defaults of Accumulator.resolve(guide=True); a tolerance of 0 switches its term off."""
+    t = [GUIDED_DEFAULTS[k] if v is None else v for k, v in (("normal", normal), ("albedo", albedo), ("depth", depth))]
+    return GuidedParams(int(iterations), float(sigma), float(t[0]), float(t[1]), float(t[2]))
+
+
 class Accumulator:
     """hrt_accum: device-resident raw per-pixel sums of a tile set (the whole frame when `tiles` is None).  Passes
     add sample ranges (`add` with params.sample_offset / params.samples), and `resolve` gives the frame of the
     samples held so far.  The frame's bits depend on the pass schedule alone (include/hrt/hrt.h).  noise=True
-    (HRT_ACCUM_NOISE) also keeps the noise plane that `noise` and `refine` read."""
+    (HRT_ACCUM_NOISE) also keeps the noise plane that `noise` and `refine` read; features=True (HRT_ACCUM_FEATURES) the
+    two first-hit feature planes that `add_features` fills and `features` and `resolve(guide=...)` read."""
 
-    def __init__(self, scene: Scene, width: int, height: int, tiles=None, noise: bool = False):
+    def __init__(self, scene: Scene, width: int, height: int, tiles=None, noise: bool = False, features: bool = False):
         self.scene, self.width, self.height = scene, int(width), int(height)  # the scene must outlive the accumulator
         self.tiles = [tuple(int(v) for v in t) for t in tiles] if tiles is not None else [(0, 0, self.width, self.height)]
         self.n_pixels = sum(t[2] * t[3] for t in self.tiles)
         self.h = ctypes.c_void_p()
         arr = (Tile * max(1, len(self.tiles)))(*[Tile(*t) for t in self.tiles])
-        self.has_noise = bool(noise)
-        if noise:
+        self.has_noise, self.has_features = bool(noise), bool(features)
+        if noise or features:
+            flags = (ACCUM_NOISE if noise else 0) | (ACCUM_FEATURES if features else 0)
             _check(load().hrt_accum_create_ex(scene.h, self.width, self.height, ctypes.cast(arr, ctypes.c_void_p),
-                                              len(self.tiles), ACCUM_NOISE, ctypes.byref(self.h)))
+                                              len(self.tiles), flags, ctypes.byref(self.h)))
         else:
             _check(load().hrt_accum_create(scene.h, self.width, self.height, ctypes.cast(arr, ctypes.c_void_p),
                                            len(self.tiles), ctypes.byref(self.h)))
@@ -702,17 +735,52 @@ class Accumulator:
             if not todo:
                 return rec
 
+    def add_features(self, cam: Camera, p: RenderParams):
+        """The first-hit features of samples [p.sample_offset, p.sample_offset + p.samples) of every pixel, added to the
+        feature planes (hrt_accum_add_features): one launch, no radiance."""
+        _check(load().hrt_accum_add_features(self.h, ctypes.byref(cam), ctypes.byref(p), None))
+
+    @property
+    def feature_samples(self) -> int:
+        n = ctypes.c_uint64()
+        _check(load().hrt_accum_feature_samples(self.h, ctypes.byref(n)))
+        return n.value
+
+    def features(self):
+        """(albedo, normal): the mean feature planes as float32 shaped like `resolve`'s frame: albedo (a.xyz, the hit
+        fraction) and normal (n.xyz, the mean depth of the hits) (hrt_accum_features_host)."""
+        al, no = np.zeros(self.n_pixels * 4, np.float32), np.zeros(self.n_pixels * 4, np.float32)
+        _check(load().hrt_accum_features_host(self.h, al.ctypes.data, no.ctypes.data))
+        return self._shaped(al), self._shaped(no)
+
+    def debug_features(self):
+        """(fa, fn): the raw feature sums as (n_pixels, 4) float32 each (hrt_debug_accum_features)."""
+        fa, fn = np.zeros((self.n_pixels, 4), np.float32), np.zeros((self.n_pixels, 4), np.float32)
+        _check(load().hrt_debug_accum_features(self.h, fa.ctypes.data, fn.ctypes.data))
+        return fa, fn
+
     def resolve(self, fmt: str = "f32", denoise=None) -> np.ndarray:
         """The frame of the samples held: float32 sqrt(sum / samples) with alpha 1 shaped like hrt.render's result,
         or uint8 (the PPM rule, alpha 255); several tiles: packed (n_pixels, 4).  denoise (a noise=True accumulator):
         the frame through the variance-guided a-trous filter instead (hrt_accum_resolve_filtered_host); True means
-        dict(iterations=3, sigma=4.0), a dict overrides either value.  A preview for noisy scenes, never a default."""
+        dict(iterations=3, sigma=4.0), a dict overrides either value.  A preview for noisy scenes, never a default.
+        With the feature terms: resolve_guided."""
         out = np.zeros(self.n_pixels * 4, np.float32 if fmt == "f32" else np.uint8)
         if denoise is None or denoise is False:
             _check(load().hrt_accum_resolve_host(self.h, _ACCUM_FORMATS[fmt], out.ctypes.data))
             return self._shaped(out)
         f = filter_params(**({} if denoise is True else dict(denoise)))
         _check(load().hrt_accum_resolve_filtered_host(self.h, ctypes.byref(f), _ACCUM_FORMATS[fmt], out.ctypes.data))
+        return self._shaped(out)
+
+    def resolve_guided(self, fmt: str = "f32", denoise=None, guide=True) -> np.ndarray:
+        """resolve(fmt, denoise) through the filter WITH the feature terms (hrt_accum_resolve_guided_host), for a
+        noise=True, features=True accumulator that holds feature samples.  denoise: as resolve's, None meaning True.
+        guide: True means GUIDED_DEFAULTS, a dict(normal=, albedo=, depth=) overrides a tolerance (0: that term off)."""
+        out = np.zeros(self.n_pixels * 4, np.float32 if fmt == "f32" else np.uint8)
+        kw = {} if denoise is None or denoise is True else dict(denoise)
+        g = guided_params(**kw, **({} if guide is True else dict(guide)))
+        _check(load().hrt_accum_resolve_guided_host(self.h, ctypes.byref(g), _ACCUM_FORMATS[fmt], out.ctypes.data))
         return self._shaped(out)
 
     def merge(self, other: "Accumulator"):
@@ -784,6 +852,25 @@ def debug_filter(raster: np.ndarray, iterations: int, sigma: float, on_device: b
     _check(load().hrt_debug_filter(1 if on_device else 0, r.ctypes.data, r.shape[1], r.shape[0], int(iterations), float(sigma),
                                    out.ctypes.data))
     return out
+
+
+def debug_guided(raster: np.ndarray, albedo: np.ndarray, normal: np.ndarray, iterations: int, sigma: float, kn: float = 0.0,
+                 ka: float = 0.0, kz: float = 0.0, on_device: bool = False) -> np.ndarray:
+    """hrt_debug_guided: debug_filter for the guided filter (csrc/guided.h).  albedo, normal: the feature rasters,
+    (height, width, 4) float32 ((a.xyz, -), (n.xyz, z)); kn, ka, kz: 1 / tolerance of each term, 0: off."""
+    r = np.ascontiguousarray(raster, np.float32)
+    a, n = np.ascontiguousarray(albedo, np.float32), np.ascontiguousarray(normal, np.float32)
+    if r.ndim != 3 or r.shape[2] != 4 or a.shape != r.shape or n.shape != r.shape:
+        raise ValueError("raster, albedo and normal must be (height, width, 4) float32 of one shape")
+    out = np.zeros_like(r)
+    _check(load().hrt_debug_guided(1 if on_device else 0, r.ctypes.data, a.ctypes.data, n.ctypes.data, r.shape[1], r.shape[0],
+                                   int(iterations), float(sigma), float(kn), float(ka), float(kz), out.ctypes.data))
+    return out
+
+
+def debug_accum_features(acc: "Accumulator"):
+    """hrt_debug_accum_features: the raw feature sums (fa, fn) of an accumulator."""
+    return acc.debug_features()
 
 
 WALK_GREEDY, WALK_DP_AREA, WALK_DP_LEAVES, WALK_GREEDY_SUB, WALK_DEVICE = range(5)

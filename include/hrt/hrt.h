@@ -339,7 +339,8 @@ hrt_status hrt_accum_create(hrt_scene* s, uint32_t width, uint32_t height, const
                             hrt_accum** out);
 /* hrt_accum_create with flags (0: hrt_accum_create itself) */
 enum {
-  HRT_ACCUM_NOISE = 1 /* also keep the noise plane (f32 per pixel) that hrt_accum_noise reads: see below */
+  HRT_ACCUM_NOISE = 1,   /* also keep the noise plane (f32 per pixel) that hrt_accum_noise reads: see below */
+  HRT_ACCUM_FEATURES = 4 /* also keep the two first-hit feature planes (2 x 16 B per pixel): see below (2 is not a flag) */
 };
 hrt_status hrt_accum_create_ex(hrt_scene* s, uint32_t width, uint32_t height, const hrt_tile* tiles, uint32_t n_tiles,
                                uint32_t flags, hrt_accum** out);
@@ -470,6 +471,67 @@ hrt_status hrt_accum_resolve_filtered(hrt_accum* a, const hrt_filter_params* f, 
 /* ... into HOST memory; waits for the device as hrt_accum_resolve_host does */
 hrt_status hrt_accum_resolve_filtered_host(hrt_accum* a, const hrt_filter_params* f, int32_t format, void* out);
 
+/* ---- first-hit feature planes ----
+ * A HRT_ACCUM_FEATURES accumulator (independent of HRT_ACCUM_NOISE) keeps, beside the sums, two planes of first-hit
+ * features, packed as the sums are, zero at creation: inputs for the guided filter below or for an external denoiser.
+ * THE BIT CONTRACT of the feature planes (csrc/feature_pass.h, -ffp-contract=off, all in f32):
+ *   The features of sample k of a pixel are those of the FIRST hit of the path a radiance sample k of that pixel
+ *   traces: the same camera ray (the same draws from (seed, pixel, k)), the closest hit over the reference node stream
+ *   from t_min, a ConstantMedium drawing from its own keyed sub-stream as in a render.
+ *     hit    = 1.0f on a hit, 0.0f on a miss;
+ *     albedo = Lambertian / Isotropic: the texture's value at the hit; Metal: its albedo; Dielectric: (1, 1, 1);
+ *              DiffuseLight: the emit texture's value, unclamped; a miss: the params' background;
+ *     normal = the hit record's world-space normal, which faces the ray; (0, 0, 0) for a medium hit and a miss;
+ *     depth  = t * sqrtf(dot(d, d)) of the camera ray (origin o, direction d) on a hit, 0 on a miss.
+ *   One hrt_accum_add_features sums its samples of a pixel in index order into fa = (albedo.xyz, hit) and
+ *   fn = (normal.xyz, depth), each from 0.0f, and the planes take the pass sum as ONE addend, plane = plane + pass_sum;
+ *   hrt_accum_merge does dst + src.
+ * So the planes are a function of the feature pass schedule alone: they never depend on the tile split, the device
+ * count or the radiance passes.  A feature pass never touches the sums, m2, K or the radiance ranges, and every other
+ * call returns the bits it would have returned.  The accumulator keeps the feature samples it holds as its own sorted,
+ * disjoint, coalesced range list (every feature pass covers every tile); the frame identity is shared with the radiance
+ * passes, and the first call of either kind fixes it.  Plans that are approximate (HRT_RENDER_FAST_CULL,
+ * HRT_RENDER_SAH) are HRT_ERR_UNSUPPORTED.  hrt_accum_reset clears planes and ranges; hrt_accum_merge needs both sides
+ * to have the flag (HRT_ERR_INVALID_ARG otherwise) and adds planes and ranges under the same disjointness rule;
+ * hrt_accum_download / _upload carry the sums only and leave the feature planes alone. */
+/* Samples [p->sample_offset, + p->samples) of every pixel of every tile: one launch.  An overlap with a held feature
+ * range, samples == 0 or an end above 2^32: HRT_ERR_INVALID_ARG; no HRT_ACCUM_FEATURES: HRT_ERR_STATE; nothing changes. */
+hrt_status hrt_accum_add_features(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, void* stream);
+hrt_status hrt_accum_feature_samples(const hrt_accum* a, uint64_t* samples);
+/* The mean planes of the NF feature samples held, packed, 16 B per pixel each, into DEVICE memory; either pointer may
+ * be NULL, not both.  With inv = 1.0f / (float)NF: albedo = (fa.xyz * inv, fa.w * inv) (w: the hit fraction);
+ * normal = (fn.xyz * inv, z), z = fa.w > 0 ? fn.w * (1.0f / fa.w) : 0 (the mean depth of the hits).  No feature
+ * samples: HRT_ERR_STATE. */
+hrt_status hrt_accum_features(hrt_accum* a, void* d_albedo, void* d_normal, void* stream);
+/* ... into HOST memory; waits for the device */
+hrt_status hrt_accum_features_host(hrt_accum* a, float* albedo, float* normal);
+
+/* ---- feature-guided preview filter ----
+ * hrt_accum_resolve_filtered with edge-stopping terms on the mean feature planes, for an accumulator created with
+ * HRT_ACCUM_NOISE | HRT_ACCUM_FEATURES that holds at least one feature sample (and meets the filtered resolve's
+ * preconditions; HRT_ERR_STATE otherwise).
+ * THE BIT CONTRACT of the guided frame (csrc/guided.h): exactly the filtered frame's iteration (the same domain, absent
+ * pixels, prefiltered variance, r, tap order, H, sv and sw).  After the luminance term e = (t * t)^2 of a tap q at
+ * pixel p the ENABLED terms follow in this order, with k_f = 1.0f / tolerance_f computed once on the host:
+ *   normal: d = ((dx * dx + dy * dy) + dz * dz) of n_q - n_p; t = at_least(1.0f - d * k_n, 0); e = e * (t * t);
+ *   albedo: the same on a_q - a_p with k_a;
+ *   depth:  d = fabsf(z_q - z_p) / ((z_q + z_p) + 1e-6f); t = at_least(1.0f - d * k_z, 0); e = e * (t * t);
+ * (a, n, z: the mean planes of hrt_accum_features, constant across iterations).  A tolerance of 0 switches its term
+ * off: the term is skipped, not multiplied by one, so with all three 0 the frame equals hrt_accum_resolve_filtered's
+ * bit for bit.  A tolerance above 0 is the feature distance at which the term's weight reaches 0; negative or NaN is
+ * HRT_ERR_INVALID_ARG.  The frame is a function of the sums, m2, (N, K) per tile, the feature planes and the covered
+ * pixel set: it does not depend on the tile cut, and the resolve writes none of them.  Two further rasters of 16 B per
+ * pixel of the tiles' bounding box are allocated by the first guided resolve and freed with the accumulator. */
+typedef struct hrt_guided_params hrt_guided_params;
+struct hrt_guided_params { /* 20 bytes */
+  uint32_t iterations;         /* as hrt_filter_params */
+  float sigma;                 /* as hrt_filter_params */
+  float normal, albedo, depth; /* tolerances; 0: the term is off */
+};
+hrt_status hrt_accum_resolve_guided(hrt_accum* a, const hrt_guided_params* g, int32_t format, void* d_out, void* stream);
+/* ... into HOST memory; waits for the device as hrt_accum_resolve_host does */
+hrt_status hrt_accum_resolve_guided_host(hrt_accum* a, const hrt_guided_params* g, int32_t format, void* out);
+
 /* ---- diagnostics ---- */
 /* Device occupancy / layout facts of the committed scene (for DESIGN/bench). */
 typedef struct hrt_scene_info {
@@ -593,6 +655,14 @@ hrt_status hrt_debug_accum_moments(hrt_accum* a, float* m2_out);
  * an absent pixel comes out as it went in.  1 <= width, height <= 65535. */
 hrt_status hrt_debug_filter(int32_t on_device, const float* raster, uint32_t width, uint32_t height, uint32_t iterations,
                             float sigma, float* out);
+/* hrt_debug_filter for the guided filter (csrc/guided.h): albedo and normal are the two feature rasters, width x
+ * height x 4 f32 ((a.xyz, -) and (n.xyz, z)), read at present pixels only; kn, ka, kz are the terms' 1 / tolerance
+ * (0: off; negative or NaN: HRT_ERR_INVALID_ARG). */
+hrt_status hrt_debug_guided(int32_t on_device, const float* raster, const float* albedo, const float* normal, uint32_t width,
+                            uint32_t height, uint32_t iterations, float sigma, float kn, float ka, float kz, float* out);
+/* The raw feature sums (fa, fn) of a HRT_ACCUM_FEATURES accumulator (n_pixels x 4 f32 each, packed as the tiles are)
+ * into host memory, after a device synchronisation: for the tests that hold the planes to their bit contract. */
+hrt_status hrt_debug_accum_features(hrt_accum* a, float* fa_out, float* fn_out);
 /* One builder of the sphere walk stream's hierarchy on n bare leaf boxes (n x 6 floats: min
  * xyz, max xyz), the code commit runs: builder 0 the host's greedy split, 1 the host's DP over 2 x half area, 2 the
  * host's DP over half area x leaves, 3 the greedy split with the DP (1) on ranges of at most dp_sub leaves, 4 the

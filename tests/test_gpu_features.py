@@ -1,0 +1,491 @@
+"""The first-hit feature planes and the feature-guided filter on the GPU: features.hip and guided.hip through
+hrt.Accumulator(features=True), the bit contracts of include/hrt/hrt.h.
+
+Input A = `random` (scene seed 1, render seed 7) at 64x36 in 16-px tiles (its top tile row is 4 px high), radiance
+passes [(0,40),(40,110),(110,126)] (tests/test_gpu_filter.py), feature passes [(0,5),(5,16)]; Cornell at 32x32 in 16-px
+tiles.  The device planes are held to tests/native/feature_sim.hip (the same per-lane code on the host), which
+tests/test_features_host.py holds to the independent restatement and to the oracle."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+
+import feature_sim as FS
+import filter_restated as FR
+import guided_restated as R
+import hrt
+from oracle import oracle as O
+
+SEED = 7
+FLOOR = 0.05
+F = np.float32
+W, H = 64, 36
+PASSES = [(0, 40), (40, 110), (110, 126)]
+FPASSES = [(0, 5), (5, 16)]
+RAGGED = [(0, 0, 37, 36), (37, 0, 27, 9), (37, 9, 27, 27)]
+DENOISE = dict(iterations=3, sigma=4)
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def u32(a):
+    return np.ascontiguousarray(a, F).view(np.uint32)
+
+
+_scenes = {}
+
+
+@pytest.fixture(scope="module")
+def scene(earth):
+    def get(name):
+        if name not in _scenes:
+            s = hrt.preset(name, 1, earth)
+            s.commit()
+            _scenes[name] = s
+        return _scenes[name]
+
+    yield get
+    for s in _scenes.values():
+        s.close()
+    _scenes.clear()
+
+
+@pytest.fixture(scope="module")
+def sim(tmp_path_factory):
+    return FS.build(tmp_path_factory)
+
+
+def setup(s, w, h, spp, offset=0, seed=SEED, flags=0):
+    cam = hrt.preset_camera(s.info, w, h)
+    return cam, hrt.params(w, h, spp, 50, seed, tuple(s.info.background), sample_offset=offset, flags=flags)
+
+
+def tiles_of(w, h, tiles):
+    return hrt.tile_grid(w, h, 16) if tiles == "grid" else tiles
+
+
+def accumulator(s, w, h, ranges=(), franges=(), noise=True, features=True, tiles="grid"):
+    a = hrt.Accumulator(s, w, h, tiles_of(w, h, tiles), noise=noise, features=features)
+    for b, e in ranges:
+        a.add(*setup(s, w, h, e - b, offset=b))
+    for b, e in franges:
+        a.add_features(*setup(s, w, h, e - b, offset=b))
+    return a
+
+
+def unpack(a, px, w, h):
+    frame = np.zeros((h, w, px.shape[-1]), px.dtype)
+    off = 0
+    for x, y, tw, th in a.tiles:
+        frame[y:y + th, x:x + tw] = px[off:off + tw * th].reshape(th, tw, -1)
+        off += tw * th
+    return frame
+
+
+def planes(a, w, h):
+    """The raw sums as one (h, w, 8) raster (pixels no tile covers: zero)."""
+    fa, fn = a.debug_features()
+    return unpack(a, np.concatenate([fa, fn], axis=1), w, h)
+
+
+def scales_of(a):
+    return [FR.tile_scales(r.samples, r.chunks) for r in a.noise(FLOOR)]
+
+
+def _raises(status, fn):
+    with pytest.raises(hrt.HrtError) as e:
+        fn()
+    assert e.value.status == status, e.value
+
+
+# ------------------------------------------------------------------------------------------ 1. the planes
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,w,h,fpasses", [("random", W, H, FPASSES), ("cornell", 32, 32, FPASSES), ("cornell_smoke", 32, 32, [(0, 4)]),
+                                              ("earth", 32, 32, [(0, 4)]), ("features", 32, 32, [(0, 4)])])
+def test_device_planes_equal_feature_sim(scene, sim, name, w, h, fpasses):
+    """Device and host run the same per-lane code under -ffp-contract=off, so the planes are asserted EQUAL, every
+    value of every pixel (fa.w and the constant albedos among them), not merely within a bound."""
+    s = scene(name)
+    a = accumulator(s, w, h, franges=fpasses, noise=False)
+    assert a.feature_samples == sum(e - b for b, e in fpasses)
+    cam = hrt.preset_camera(s.info, w, h)
+    want = FS.planes(sim, s, cam, lambda n, off: setup(s, w, h, n, offset=off)[1], fpasses)
+    got = planes(a, w, h)
+    assert np.isfinite(got).all() and got[..., 3].max() > 0
+    assert np.array_equal(got[..., 3], want[..., 3])
+    assert np.array_equal(u32(got), u32(want)), np.abs(got - want).max()
+    # the mean planes
+    al, no = a.features()
+    fa, fn = a.debug_features()
+    wal, wno = R.mean_planes(fa, fn, a.feature_samples)
+    assert np.array_equal(u32(al), u32(wal)) and np.array_equal(u32(no), u32(wno))
+    a.close()
+
+
+@pytest.mark.gpu
+def test_miss_counts_equal_the_oracles(scene):
+    s = scene("random")
+    a = accumulator(s, W, H, franges=[(0, 16)], noise=False)
+    ref, _ = O.OracleScene(hrt.PRESETS["random"], 1).render(W, H, 16, 1, seed=SEED, threads=8)
+    m = (ref[..., :3].astype(np.float64) ** 2) * 16 / np.array(s.info.background, np.float64)
+    assert np.abs(m - np.rint(m)).max() <= 3e-6 and (np.rint(m) == np.rint(m[..., :1])).all()
+    assert np.array_equal(16 - planes(a, W, H)[..., 3], np.rint(m[..., 0]))
+    a.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,w,h", [("random", W, H), ("cornell_smoke", 32, 32)])
+def test_one_sample_pass_equals_trace_path(scene, name, w, h):
+    """fn.w is t * |d| of hrt.trace_path's segment 0 and fa.w is winner != NONE, bit for bit: the same code on the
+    same device."""
+    s = scene(name)
+    for sample in (0, 3):
+        a = accumulator(s, w, h, franges=[(sample, sample + 1)], noise=False)
+        got = planes(a, w, h)
+        cam, p = setup(s, w, h, 1, offset=sample)
+        hits = 0
+        for x, y in [(3, 2), (20, 10), (45 % w, 22), (5, 30), (33 % w, 17), (60 % w, 2), (31, 12), (w - 1, h - 1), (0, 0), (16, 16), (15, 4),
+                     (w // 2, h // 2)]:
+            segs, _ = hrt.trace_path(s, cam, p, x, y, 0)
+            o, d, _, t, winner = segs[0]
+            hit = winner != 0xFFFFFFFF
+            hits += hit
+            assert got[y, x, 3] == (1.0 if hit else 0.0)
+            depth = F(t) * np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2], dtype=F) if hit else F(0)
+            assert F(depth).view(np.uint32) == got[y, x, 7].view(np.uint32), (x, y, depth, got[y, x, 7])
+        assert 0 < hits
+        a.close()
+
+
+@pytest.mark.gpu
+def test_planes_do_not_depend_on_the_tile_split(scene, monkeypatch):
+    s = scene("random")
+    grid, whole, ragged = (accumulator(s, W, H, franges=FPASSES, noise=False, tiles=t) for t in ("grid", None, RAGGED))
+    want = planes(whole, W, H)
+    assert np.array_equal(u32(planes(grid, W, H)), u32(want)) and np.array_equal(u32(planes(ragged, W, H)), u32(want))
+    al, no = whole.features()
+    assert al.shape == (H, W, 4) and np.array_equal(u32(unpack(grid, grid.features()[1], W, H)), u32(no))
+    g16 = hrt.tile_grid(W, H, 16)
+    sub = accumulator(s, W, H, franges=FPASSES, noise=False, tiles=[g16[t] for t in (0, 5, 10)])
+    fa, fn = sub.debug_features()
+    assert np.array_equal(u32(np.concatenate([fa, fn], 1)), u32(np.concatenate([want[y:y + th, x:x + tw].reshape(-1, 8) for x, y, tw, th in sub.tiles])))
+    # the A/B knob's block shapes (read when the accumulator is created) are bit-identical variants
+    for bw in ("64", "32", "1"):
+        monkeypatch.setenv("HRT_FEATURE_BLOCK_W", bw)
+        shaped = accumulator(s, W, H, franges=FPASSES, noise=False, tiles=RAGGED)
+        monkeypatch.delenv("HRT_FEATURE_BLOCK_W")
+        assert np.array_equal(u32(planes(shaped, W, H)), u32(want)), bw
+        shaped.close()
+    for x in (grid, whole, ragged, sub):
+        x.close()
+
+
+@pytest.mark.gpu
+def test_feature_passes_change_nothing_else(scene):
+    s = scene("random")
+    plain = accumulator(s, W, H, PASSES, features=False)
+    mixed = hrt.Accumulator(s, W, H, hrt.tile_grid(W, H, 16), noise=True, features=True)
+    mixed.add_features(*setup(s, W, H, 11, offset=5))          # the later feature range first, before any radiance
+    mixed.add(*setup(s, W, H, 40, offset=0))
+    mixed.add(*setup(s, W, H, 70, offset=40))
+    mixed.add_features(*setup(s, W, H, 5, offset=0))
+    mixed.add(*setup(s, W, H, 16, offset=110))
+    assert mixed.samples == 126 and mixed.feature_samples == 16
+    assert mixed.download()[1] == plain.download()[1]
+    for get in (lambda x: x.download()[0], lambda x: x.moments(), lambda x: x.resolve(), lambda x: x.noise(FLOOR, error_map=True)[1],
+                lambda x: x.resolve(denoise=DENOISE), lambda x: x.resolve("rgba8", denoise=DENOISE)):
+        assert np.array_equal(get(mixed).view(np.uint8), get(plain).view(np.uint8))
+    assert [(r.mean, r.max, r.samples, r.chunks) for r in mixed.noise(FLOOR)] == [(r.mean, r.max, r.samples, r.chunks) for r in plain.noise(FLOOR)]
+    # the planes are those of the schedule (5,16) then (0,5), whatever lay between: plane = (0 + s(5,16)) + s(0,5)
+    alone = accumulator(s, W, H, franges=[(5, 16), (0, 5)], noise=False)
+    assert np.array_equal(u32(planes(mixed, W, H)), u32(planes(alone, W, H)))
+    order = accumulator(s, W, H, franges=[(0, 16)], noise=False)   # one pass of the same samples: another schedule
+    assert not np.array_equal(u32(planes(order, W, H)), u32(planes(alone, W, H)))
+    # reset clears planes and ranges
+    mixed.reset()
+    assert mixed.feature_samples == 0 and mixed.samples == 0 and not planes(mixed, W, H).any()
+    mixed.add_features(*setup(s, W, H, 5, offset=0, seed=9))  # and the identity
+    for x in (plain, mixed, alone, order):
+        x.close()
+
+
+@pytest.mark.gpu
+def test_merge(scene):
+    s = scene("random")
+    a, b = accumulator(s, W, H, [(0, 40)], [(0, 5)]), accumulator(s, W, H, [(40, 110)], [(5, 16)])
+    both = accumulator(s, W, H, [(0, 40), (40, 110)], FPASSES)
+    before = planes(a, W, H), a.download()[0]
+    _raises(hrt.ERR_INVALID_ARG, lambda: a.merge(accumulator(s, W, H, [(200, 216)], [(4, 6)])))      # feature ranges overlap
+    _raises(hrt.ERR_INVALID_ARG, lambda: a.merge(accumulator(s, W, H, [(0, 16)], [(30, 31)])))       # radiance ranges overlap
+    _raises(hrt.ERR_INVALID_ARG, lambda: a.merge(accumulator(s, W, H, [(200, 216)], features=False)))  # mixed flags
+    _raises(hrt.ERR_INVALID_ARG, lambda: accumulator(s, W, H, [(200, 216)], features=False).merge(a))
+    assert np.array_equal(u32(planes(a, W, H)), u32(before[0])) and np.array_equal(u32(a.download()[0]), u32(before[1]))
+    assert a.feature_samples == 5 and a.samples == 40
+    a.merge(b)
+    assert a.feature_samples == 16 and a.samples == 110
+    assert np.array_equal(u32(planes(a, W, H)), u32(planes(both, W, H)))
+    assert np.array_equal(u32(a.download()[0]), u32(both.download()[0])) and np.array_equal(u32(a.moments()), u32(both.moments()))
+    only = accumulator(s, W, H, franges=[(16, 20)])        # feature samples alone merge too
+    a.merge(only)
+    assert a.feature_samples == 20 and a.samples == 110
+    for x in (a, b, both, only):
+        x.close()
+
+
+# ------------------------------------------------------------------------------------------ 2. the guided filter
+def rasters(w, h, absent):
+    import test_guided_host as TG
+
+    return TG.rasters(w, h, absent)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("h", [7, 8, 9, 40])
+@pytest.mark.parametrize("w", [31, 32, 33, 70])
+def test_device_guided_equals_host(w, h, monkeypatch):
+    """As tests/test_gpu_filter.py's: 5 iterations pass the steps that stage the colour and feature planes in LDS
+    (1, 2, 4) and nothing (8, 16), each as an inner and as the last iteration."""
+    for absent in (False, True):
+        r, a, n = rasters(w, h, absent)
+        for it in (1, 2, 3, 4, 5):
+            k = dict(kn=2.0, ka=10.0, kz=10.0)
+            host, dev = hrt.debug_guided(r, a, n, it, 4.0, **k), hrt.debug_guided(r, a, n, it, 4.0, on_device=True, **k)
+            assert np.array_equal(u32(dev), u32(host)), (w, h, absent, it)
+        for k in (dict(kn=2.0), dict(ka=10.0), dict(kz=10.0), {}):
+            assert np.array_equal(u32(hrt.debug_guided(r, a, n, 3, 0.5, on_device=True, **k)), u32(hrt.debug_guided(r, a, n, 3, 0.5, **k)))
+    # the staging knob's variants are bit-identical: features never staged, and staged up to step 2 alone
+    r, a, n = rasters(w, h, True)
+    want = hrt.debug_guided(r, a, n, 4, 4.0, kn=2.0, ka=10.0, kz=10.0)
+    for v in ("0", "2"):
+        monkeypatch.setenv("HRT_GUIDED_LDS_STEP", v)
+        assert np.array_equal(u32(hrt.debug_guided(r, a, n, 4, 4.0, kn=2.0, ka=10.0, kz=10.0, on_device=True)), u32(want))
+
+
+def restated(a, w, h, it, sigma, tol, sums=None):
+    sums, m2 = a.download()[0] if sums is None else sums, a.moments()
+    al, no = a.features()
+    return R.guided_frame(sums, m2, a.tiles, scales_of(a), al.reshape(-1, 4), no.reshape(-1, 4), w, h, it, sigma, tol)
+
+
+@pytest.mark.gpu
+def test_guided_resolve_equals_the_restatement_and_changes_nothing(scene):
+    s = scene("random")
+    a = accumulator(s, W, H, PASSES, FPASSES)
+    state = a.download(), a.moments(), a.resolve(), a.debug_features(), a.resolve(denoise=DENOISE)
+    tol = dict(hrt.GUIDED_DEFAULTS)
+    for it in (1, 3, 5):
+        got = a.resolve_guided(denoise=dict(iterations=it), guide=True)
+        assert got.shape == (W * H, 4) and got.dtype == F and (got[:, 3] == 1).all()
+        assert np.array_equal(u32(got), u32(restated(a, W, H, it, 4.0, tol))), it
+    g3 = a.resolve_guided(guide=True)                                  # guide alone: denoise=True
+    assert np.array_equal(u32(g3), u32(restated(a, W, H, 3, 4.0, tol))) and not np.array_equal(u32(g3), u32(state[4]))
+    assert np.array_equal(a.resolve_guided("rgba8", guide=True), FR.quantize(g3))
+    for one in (dict(normal=0.5, albedo=0, depth=0), dict(normal=0, albedo=0.1, depth=0), dict(normal=0, albedo=0, depth=0.1)):
+        assert np.array_equal(u32(a.resolve_guided(denoise=dict(sigma=2.0), guide=one)), u32(restated(a, W, H, 3, 2.0, one)))
+    off = dict(normal=0, albedo=0, depth=0)
+    for fmt in ("f32", "rgba8"):
+        assert np.array_equal(a.resolve_guided(fmt, denoise=DENOISE, guide=off), a.resolve(fmt, denoise=DENOISE))
+    # the accumulator is as it was
+    again = a.download(), a.moments(), a.resolve(), a.debug_features(), a.resolve(denoise=DENOISE)
+    assert again[0][1] == state[0][1] and np.array_equal(u32(again[0][0]), u32(state[0][0]))
+    for x, y in zip(again[1:3] + again[3] + again[4:], state[1:3] + state[3] + state[4:]):
+        assert np.array_equal(u32(x), u32(y))
+    a.close()
+
+
+@pytest.mark.gpu
+def test_guided_frame_does_not_depend_on_the_tile_split(scene):
+    s = scene("random")
+    tiled, whole, ragged = (accumulator(s, W, H, PASSES, FPASSES, tiles=t) for t in ("grid", None, RAGGED))
+    for fmt, kw in (("f32", dict(guide=True)), ("rgba8", dict(denoise=dict(iterations=5, sigma=2.0), guide=dict(normal=0.25)))):
+        fw = whole.resolve_guided(fmt, **kw)
+        assert fw.shape == (H, W, 4)
+        assert np.array_equal(unpack(tiled, tiled.resolve_guided(fmt, **kw), W, H), fw)
+        assert np.array_equal(unpack(ragged, ragged.resolve_guided(fmt, **kw), W, H), fw)
+    for x in (tiled, whole, ragged):
+        x.close()
+
+
+@pytest.mark.gpu
+def test_guided_tiles_that_hold_different_passes_and_subsets(scene):
+    s = scene("random")
+    subset = [1, 4, 11]
+    first, both = accumulator(s, W, H, [(0, 40)], features=False), accumulator(s, W, H, [(0, 40), (40, 80)], features=False)
+    sub = accumulator(s, W, H, [(0, 40)], FPASSES)
+    sub.add(*setup(s, W, H, 40, offset=40), tiles=subset)
+    assert len(set(scales_of(sub))) == 2
+    # a tile's sums are those of a uniform accumulator with that tile's passes (tests/test_gpu_filter.py)
+    sums, off = first.download()[0].copy(), 0
+    for t, (_, _, tw, th) in enumerate(sub.tiles):
+        if t in subset:
+            sums[off:off + tw * th] = both.download()[0][off:off + tw * th]
+        off += tw * th
+    for it in (1, 3):
+        got = sub.resolve_guided(denoise=dict(iterations=it), guide=True)
+        assert np.array_equal(u32(got), u32(restated(sub, W, H, it, 4.0, hrt.GUIDED_DEFAULTS, sums))), it
+    for x in (first, both, sub):
+        x.close()
+    grid = hrt.tile_grid(W, H, 16)
+    for subset in ([0, 1, 4, 5], [0, 5, 10]):                  # [0, 5, 10]: absent pixels inside the bounding box
+        a = accumulator(s, W, H, PASSES, FPASSES, tiles=[grid[t] for t in subset])
+        for it in (3, 5):
+            assert np.array_equal(u32(a.resolve_guided(denoise=dict(iterations=it), guide=True)), u32(restated(a, W, H, it, 4.0, hrt.GUIDED_DEFAULTS))), it
+        a.close()
+
+
+# ------------------------------------------------------------------------------------------ 3. quality
+_ref = {}
+
+
+def reference(name, earth):
+    """The oracle's 4096-spp frame of another seed (1234), as tests/test_gpu_filter.py builds Cornell's.  Input A's takes
+    a minute on the CPU, so it is a fixture: tests/golden/random_64x36_4096spp_seed1234.npy holds
+    O.OracleScene(PRESETS["random"], 1, earth).render(64, 36, 4096, 50, seed=1234)[0][..., :3] as float32."""
+    if name not in _ref:
+        if name == "random":
+            _ref[name] = np.load(os.path.join(HERE, "golden", "random_64x36_4096spp_seed1234.npy")).astype(np.float64)
+        else:
+            rgb, _ = O.OracleScene(hrt.PRESETS[name], 1, earth).render(32, 32, 4096, 50, seed=1234)
+            _ref[name] = np.asarray(rgb[..., :3], np.float64)
+    return _ref[name]
+
+
+def rmse_ratios(a, w, h, ref):
+    rm = lambda px: np.sqrt(((unpack(a, px, w, h)[..., :3].astype(np.float64) - ref) ** 2).mean())  # noqa: E731
+    plain, filt, guided = rm(a.resolve()), rm(a.resolve(denoise=DENOISE)), rm(a.resolve_guided(denoise=DENOISE, guide=True))
+    print(f"\nRMSE plain {plain:.5f}, variance-only {filt:.5f}, guided {guided:.5f}: guided / variance-only {guided / filt:.3f}, "
+          f"guided / plain {guided / plain:.3f}")
+    return guided / filt, guided / plain
+
+
+def bound(r_cpu):
+    return r_cpu + (1 - r_cpu) / 2
+
+
+@pytest.mark.gpu
+def test_guided_filter_quality_on_cornell(scene, earth):
+    """`cornell` at 32x32 after passes (0,40),(40,80) and a 16-sample feature pass, display-unit RMSE against the
+    oracle's 4096-spp frame of seed 1234, with the default tolerances (0.1, 0.1, 0.1).  Computed on the CPU from the
+    oracle's own chunk sums (the library's chunk schedule, the restatement, feature_sim's planes): plain 0.14647,
+    variance-only 0.08630, guided 0.08204, so r_cpu(guided / variance-only) = 0.951 and r_cpu(guided / plain) = 0.560.
+    Asserted: ratio <= r_cpu + (1 - r_cpu) / 2, the margin for the library's own sums and f32 moments."""
+    s = scene("cornell")
+    a = accumulator(s, 32, 32, [(0, 40), (40, 80)], [(0, 16)])
+    gf, gp = rmse_ratios(a, 32, 32, reference("cornell", earth))
+    assert gf <= bound(0.951) and gp <= bound(0.560)
+    a.close()
+
+
+@pytest.mark.gpu
+def test_guided_filter_quality_on_input_a(scene, earth):
+    """Input A, where the variance-only filter is worse than no filter.  On the CPU as above: plain 0.01687,
+    variance-only 0.03682, guided 0.01681, so r_cpu(guided / variance-only) = 0.457 (below 0.8: asserted) and
+    r_cpu(guided / plain) = 0.997: on a frame this clean the guided filter gains next to nothing, but with these
+    tolerances it no longer loses (with the starting values 0.5, 0.1, 0.1 the second ratio was 1.016)."""
+    s = scene("random")
+    a = accumulator(s, W, H, PASSES, FPASSES)
+    gf, gp = rmse_ratios(a, W, H, reference("random", earth))
+    assert gf <= bound(0.457) and gp <= bound(0.997)
+    a.close()
+
+
+# ------------------------------------------------------------------------------------------ 4. errors, streams
+@pytest.mark.gpu
+def test_errors_change_nothing(scene):
+    s = scene("random")
+    a = accumulator(s, W, H, [(0, 40)], [(0, 5)])
+    no_feat = accumulator(s, W, H, [(0, 40)], features=False)
+    no_noise = accumulator(s, W, H, [(0, 40)], [(0, 5)], noise=False)
+    no_fsamples = accumulator(s, W, H, [(0, 40)])
+    one = accumulator(s, W, H, [(0, 16)], [(0, 5)])              # K = 1
+    overlap = accumulator(s, W, H, [(0, 40)], [(0, 5)], tiles=[(0, 0, 20, 20), (16, 16, 20, 20)])
+    state = {x: (x.download()[0], x.resolve()) for x in (a, no_feat, no_noise, no_fsamples, one, overlap)}
+    feats = {x: x.debug_features() for x in (a, no_noise, one, overlap)}
+
+    def unchanged():
+        for x, (sums, px) in state.items():
+            assert np.array_equal(u32(x.download()[0]), u32(sums)) and np.array_equal(u32(x.resolve()), u32(px))
+        for x, (fa, fn) in feats.items():
+            assert np.array_equal(u32(x.debug_features()[0]), u32(fa)) and np.array_equal(u32(x.debug_features()[1]), u32(fn))
+        assert a.feature_samples == 5 and no_fsamples.feature_samples == 0 and a.samples == 40
+
+    for x in (no_feat, no_noise, no_fsamples, one):
+        for fmt in ("f32", "rgba8"):
+            _raises(hrt.ERR_STATE, lambda: x.resolve_guided(fmt, guide=True))
+    for _ in range(2):
+        _raises(hrt.ERR_UNSUPPORTED, lambda: overlap.resolve_guided(guide=True))
+    _raises(hrt.ERR_STATE, lambda: no_feat.add_features(*setup(s, W, H, 4, offset=8)))
+    _raises(hrt.ERR_STATE, lambda: no_feat.features())
+    _raises(hrt.ERR_STATE, lambda: no_feat.feature_samples)
+    _raises(hrt.ERR_STATE, lambda: no_feat.debug_features())
+    _raises(hrt.ERR_STATE, lambda: no_fsamples.features())
+    for it in (0, 6):
+        _raises(hrt.ERR_INVALID_ARG, lambda: a.resolve_guided(denoise=dict(iterations=it), guide=True))
+    for sigma in (0.0, -4.0, float("nan")):
+        _raises(hrt.ERR_INVALID_ARG, lambda: a.resolve_guided(denoise=dict(sigma=sigma), guide=True))
+    for key in ("normal", "albedo", "depth"):
+        for bad in (-0.1, float("nan")):
+            _raises(hrt.ERR_INVALID_ARG, lambda: a.resolve_guided(guide={key: bad}))
+    _raises(hrt.ERR_INVALID_ARG, lambda: no_feat.resolve_guided(guide=dict(normal=-1)))     # argument errors come first
+    # feature ranges: overlap, empty, an end above 2^32, another identity
+    _raises(hrt.ERR_INVALID_ARG, lambda: a.add_features(*setup(s, W, H, 4, offset=3)))
+    _raises(hrt.ERR_INVALID_ARG, lambda: a.add_features(*setup(s, W, H, 0, offset=8)))
+    _raises(hrt.ERR_INVALID_ARG, lambda: a.add_features(*setup(s, W, H, 16, offset=2 ** 32 - 8)))
+    _raises(hrt.ERR_INVALID_ARG, lambda: a.add_features(*setup(s, W, H, 4, offset=8, seed=SEED + 1)))
+    # approximate plans, on an accumulator whose identity they would fix
+    for flags in (hrt.RENDER_FAST_CULL, hrt.RENDER_SAH, hrt.RENDER_FAST_CULL | hrt.RENDER_SAH):
+        fresh = hrt.Accumulator(s, W, H, hrt.tile_grid(W, H, 16), features=True)
+        _raises(hrt.ERR_UNSUPPORTED, lambda: fresh.add_features(*setup(s, W, H, 4, flags=flags)))
+        assert fresh.feature_samples == 0 and not planes(fresh, W, H).any()
+        fresh.add_features(*setup(s, W, H, 4))                    # the identity was not fixed
+        fresh.close()
+    # null pointers
+    L, g = hrt.load(), hrt.guided_params()
+    cam, p = setup(s, W, H, 4, offset=8)
+    out = np.zeros(W * H * 4, F)
+    assert L.hrt_accum_resolve_guided_host(a.h, None, hrt.ACCUM_F32, out.ctypes.data) == hrt.ERR_INVALID_ARG
+    assert L.hrt_accum_resolve_guided_host(a.h, ctypes.byref(g), hrt.ACCUM_F32, None) == hrt.ERR_INVALID_ARG
+    assert L.hrt_accum_resolve_guided_host(None, ctypes.byref(g), hrt.ACCUM_F32, out.ctypes.data) == hrt.ERR_INVALID_ARG
+    assert L.hrt_accum_resolve_guided_host(a.h, ctypes.byref(g), 2, out.ctypes.data) == hrt.ERR_INVALID_ARG
+    assert L.hrt_accum_resolve_guided(a.h, ctypes.byref(g), hrt.ACCUM_F32, None, None) == hrt.ERR_INVALID_ARG
+    assert L.hrt_accum_add_features(a.h, None, ctypes.byref(p), None) == hrt.ERR_INVALID_ARG
+    assert L.hrt_accum_add_features(a.h, ctypes.byref(cam), None, None) == hrt.ERR_INVALID_ARG
+    assert L.hrt_accum_add_features(None, ctypes.byref(cam), ctypes.byref(p), None) == hrt.ERR_INVALID_ARG
+    assert L.hrt_accum_features_host(a.h, None, None) == hrt.ERR_INVALID_ARG
+    assert L.hrt_accum_features(a.h, None, None, None) == hrt.ERR_INVALID_ARG
+    assert L.hrt_accum_feature_samples(a.h, None) == hrt.ERR_INVALID_ARG
+    assert L.hrt_debug_accum_features(a.h, None, out.ctypes.data) == hrt.ERR_INVALID_ARG
+    assert not out.any()
+    unchanged()
+    assert L.hrt_accum_features_host(a.h, out.ctypes.data, None) == hrt.OK and out.any()   # either plane alone
+    assert a.resolve_guided(guide=True).shape == (W * H, 4)
+    for x in (a, no_feat, no_noise, no_fsamples, one, overlap):
+        x.close()
+
+
+@pytest.mark.gpu
+def test_feature_pass_and_guided_resolve_on_a_stream_into_device_memory(scene):
+    import torch
+
+    s = scene("random")
+    ref = accumulator(s, W, H, PASSES, FPASSES)
+    want, (wal, wno) = ref.resolve_guided(guide=True), ref.features()
+    a = accumulator(s, W, H, PASSES)
+    L, g = hrt.load(), hrt.guided_params()
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        for b, e in FPASSES:
+            cam, p = setup(s, W, H, e - b, offset=b)
+            assert L.hrt_accum_add_features(a.h, ctypes.byref(cam), ctypes.byref(p), ctypes.c_void_p(stream.cuda_stream)) == hrt.OK
+        for _ in range(2):
+            buf = torch.zeros(W * H * 4, dtype=torch.float32, device="cuda")
+            al, no = torch.zeros_like(buf), torch.zeros_like(buf)
+            assert L.hrt_accum_resolve_guided(a.h, ctypes.byref(g), hrt.ACCUM_F32, ctypes.c_void_p(buf.data_ptr()),
+                                              ctypes.c_void_p(stream.cuda_stream)) == hrt.OK
+            assert L.hrt_accum_features(a.h, ctypes.c_void_p(al.data_ptr()), ctypes.c_void_p(no.data_ptr()),
+                                        ctypes.c_void_p(stream.cuda_stream)) == hrt.OK
+            stream.synchronize()
+            assert np.array_equal(u32(buf.cpu().numpy().reshape(-1, 4)), u32(want))
+            assert np.array_equal(u32(al.cpu().numpy().reshape(-1, 4)), u32(wal)) and np.array_equal(u32(no.cpu().numpy().reshape(-1, 4)), u32(wno))
+    a.close()
+    ref.close()

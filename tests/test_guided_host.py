@@ -1,0 +1,200 @@
+"""The feature-guided a-trous filter's arithmetic (csrc/guided.h through hrt.debug_guided on the host) against the
+independent numpy restatement (tests/guided_restated.py), without a GPU: the bit contract of include/hrt/hrt.h."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+
+import filter_restated as FR
+import guided_restated as R
+import hrt
+
+F = np.float32
+TERMS = [dict(kn=2.0), dict(ka=10.0), dict(kz=10.0), dict(kn=2.0, ka=10.0, kz=10.0)]
+
+
+def u32(a):
+    return np.ascontiguousarray(a, F).view(np.uint32)
+
+
+def rasters(w, h, absent):
+    """A random colour raster (as tests/test_gpu_filter.py's) with piecewise-smooth feature planes: unit-ish normals,
+    albedos in [0, 1], depths in [1, 20], plus noise, so every term's weight takes values between 0 and 1."""
+    rng = np.random.default_rng(100 * w + h + (7 if absent else 0))
+    r = np.zeros((h, w, 4), F)
+    r[..., :3] = rng.uniform(0.0, 2.0, (h, w, 3)).astype(F)
+    r[..., 3] = (10.0 ** rng.uniform(-8.0, 0.0, (h, w))).astype(F)
+    if absent:
+        gone = rng.uniform(size=(h, w)) < 0.08
+        gone[:, w // 2] = True
+        gone[h - 1, :5] = True
+        r[gone, :3] = rng.uniform(-5.0, 5.0, (int(gone.sum()), 3)).astype(F)
+        r[gone, 3] = -rng.uniform(0.5, 2.0, int(gone.sum())).astype(F)
+    region = (np.arange(w)[None, :] // 5 + np.arange(h)[:, None] // 3) % 3
+    a, n = np.zeros((h, w, 4), F), np.zeros((h, w, 4), F)
+    base_a, base_n = rng.uniform(0, 1, (3, 3)), rng.normal(size=(3, 3))
+    base_n /= np.linalg.norm(base_n, axis=1, keepdims=True)
+    a[..., :3] = (base_a[region] + rng.normal(0, 0.05, (h, w, 3))).astype(F)
+    a[..., 3] = rng.uniform(0, 1, (h, w)).astype(F)
+    n[..., :3] = (base_n[region] + rng.normal(0, 0.1, (h, w, 3))).astype(F)
+    n[..., 3] = (np.array([1.0, 5.0, 20.0])[region] * rng.uniform(0.9, 1.1, (h, w))).astype(F)
+    n[..., 3][rng.uniform(size=(h, w)) < 0.05] = 0  # pixels whose samples all missed
+    return r, a, n
+
+
+@pytest.mark.parametrize("h", [7, 8, 9, 40])
+@pytest.mark.parametrize("w", [31, 32, 33, 70])
+def test_host_guided_equals_the_restatement(w, h):
+    """31/32/33 x 7/8/9 and 70 x 40, with and without absent pixels, iterations 1..5, each term alone and all three."""
+    for absent in (False, True):
+        r, a, n = rasters(w, h, absent)
+        for k in TERMS:
+            for it in (1, 2, 3, 4, 5) if (w, h) != (70, 40) or k is TERMS[3] else (3,):
+                got, want = hrt.debug_guided(r, a, n, it, 4.0, **k), R.guided_raster(r, a, n, it, 4.0, **k)
+                assert np.array_equal(u32(got), u32(want)), (w, h, absent, k, it)
+                assert not np.array_equal(u32(got), u32(hrt.debug_filter(r, it, 4.0))), "the term changed nothing"
+
+
+@pytest.mark.parametrize("w,h", [(33, 9), (70, 40)])
+def test_all_terms_off_is_the_variance_only_filter(w, h):
+    for absent in (False, True):
+        r, a, n = rasters(w, h, absent)
+        for it in (1, 3, 5):
+            off = hrt.debug_guided(r, a, n, it, 4.0)
+            assert np.array_equal(u32(off), u32(hrt.debug_filter(r, it, 4.0)))
+            assert np.array_equal(u32(off), u32(FR.filter_raster(r, it, 4.0)))
+            assert np.array_equal(u32(R.guided_raster(r, a, n, it, 4.0)), u32(off))
+
+
+def test_restatement_plane_form_equals_a_scalar_loop():
+    """The restatement's shifted-plane form against a per-pixel loop written from the contract, on a small raster."""
+    r, a, n = rasters(13, 6, True)
+    kn, ka, kz = F(2.0), F(10.0), F(10.0)
+    src, s, sigma = r, 2, F(4.0)
+    want = R.iteration(r, a, n, s, sigma, kn, ka, kz)
+    h, w = r.shape[:2]
+    Hh = FR.H
+    with np.errstate(all="ignore"):
+        for y in range(h):
+            for x in range(w):
+                if src[y, x, 3] < 0:
+                    assert np.array_equal(u32(want[y, x]), u32(src[y, x]))
+                    continue
+                p = src[y, x]
+                lp = (p[0] + p[1]) + p[2]
+                num = den = F(0)
+                for dy in (-1, 0, 1):
+                    for dx in (-1, 0, 1):
+                        qx, qy = x + dx, y + dy
+                        if 0 <= qx < w and 0 <= qy < h and not src[qy, qx, 3] < 0:
+                            g = F(FR.G[dy + 1]) * F(FR.G[dx + 1])
+                            num, den = num + g * src[qy, qx, 3], den + g
+                rr = F(1) / (sigma * np.sqrt(num / den) + F(1e-6))
+                sc, sv, sw = [F(0)] * 3, F(0), F(0)
+                for dy in range(-2, 3):
+                    for dx in range(-2, 3):
+                        qx, qy = x + s * dx, y + s * dy
+                        if not (0 <= qx < w and 0 <= qy < h) or src[qy, qx, 3] < 0:
+                            continue
+                        q = src[qy, qx]
+                        t = F(1) - (np.abs(((q[0] + q[1]) + q[2]) - lp) * rr) * F(0.5)
+                        t = t if t > 0 else F(0)
+                        e = t * t
+                        e = e * e
+                        for plane, k in ((n, kn), (a, ka)):
+                            dd = plane[qy, qx, :3] - plane[y, x, :3]
+                            t = F(1) - ((dd[0] * dd[0] + dd[1] * dd[1]) + dd[2] * dd[2]) * k
+                            t = t if t > 0 else F(0)
+                            e = e * (t * t)
+                        zq, zp = n[qy, qx, 3], n[y, x, 3]
+                        t = F(1) - (np.abs(zq - zp) / ((zq + zp) + F(1e-6))) * kz
+                        t = t if t > 0 else F(0)
+                        e = e * (t * t)
+                        wt = (F(Hh[dy + 2]) * F(Hh[dx + 2])) * e
+                        sc = [sc[c] + wt * q[c] for c in range(3)]
+                        sv, sw = sv + (wt * wt) * q[3], sw + wt
+                got = np.array([sc[0] / sw, sc[1] / sw, sc[2] / sw, sv / (sw * sw)], F) if sw != 0 else p
+                assert np.array_equal(u32(got), u32(want[y, x])), (x, y)
+
+
+@pytest.mark.parametrize("term", ["normal", "albedo", "depth"])
+def test_a_term_keeps_two_flat_regions_apart(term):
+    """Two flat halves of equal radiance statistics that differ ONLY in one feature: with that term on (the difference
+    is beyond the tolerance) no tap crosses the border, so each half filters as if it stood alone; with it off the
+    halves mix."""
+    w, h = 24, 10
+    rng = np.random.default_rng(5)
+    r = np.zeros((h, w, 4), F)
+    r[..., :3] = rng.uniform(0.4, 0.6, (h, w, 3)).astype(F)
+    r[..., 3] = F(4)  # a power of two (the prefiltered variance is exact whatever taps are present), above the halves' contrast
+    a, n = np.zeros((h, w, 4), F), np.zeros((h, w, 4), F)
+    a[..., :3], n[..., :3], n[..., 3] = F(0.5), (F(0), F(0), F(1)), F(4)
+    left = np.arange(w) < w // 2
+    if term == "normal":
+        n[:, ~left, :3] = (F(1), F(0), F(0))       # squared distance 2, tolerance 0.5
+    elif term == "albedo":
+        a[:, ~left, :3] = F(0.9)                   # squared distance 0.48, tolerance 0.1
+    else:
+        n[:, ~left, 3] = F(8)                      # relative distance 1/3, tolerance 0.1
+    tol = {"normal": 0.5, "albedo": 0.1, "depth": 0.1}[term]
+    k = {"k" + term[0].replace("d", "z"): float(F(1) / F(tol))}
+    cut = lambda x, m: np.ascontiguousarray(x[:, m])  # noqa: E731
+    # one iteration: a tap of weight 0 adds w * c = 0 and w = 0 to the sums, which changes no bit of them (the variance
+    # prefilter has no feature term, so later iterations see the other half's v' at the border)
+    on = hrt.debug_guided(r, a, n, 1, 4.0, **k)
+    alone = [hrt.debug_guided(cut(r, m), cut(a, m), cut(n, m), 1, 4.0, **k) for m in (left, ~left)]
+    assert np.array_equal(u32(on[:, left]), u32(alone[0])) and np.array_equal(u32(on[:, ~left]), u32(alone[1]))
+    off = hrt.debug_guided(r, a, n, 1, 4.0)
+    assert not np.array_equal(u32(off[:, left]), u32(alone[0])) and not np.array_equal(u32(off[:, ~left]), u32(alone[1]))
+    assert np.array_equal(u32(on), u32(R.guided_raster(r, a, n, 1, 4.0, **k)))
+    # three iterations on halves of constant colour 0.25 and 0.75 (scaling by a power of two commutes with every
+    # rounding): on, each half keeps its colour exactly; off, the border blurs
+    r[:, left, :3], r[:, ~left, :3] = F(0.25), F(0.75)
+    on, off = hrt.debug_guided(r, a, n, 3, 4.0, **k), hrt.debug_guided(r, a, n, 3, 4.0)
+    assert (on[:, left, :3] == F(0.25)).all() and (on[:, ~left, :3] == F(0.75)).all()
+    assert (off[:, w // 2 - 1, :3] > F(0.3)).all() and (off[:, w // 2, :3] < F(0.7)).all()
+    assert np.array_equal(u32(on), u32(R.guided_raster(r, a, n, 3, 4.0, **k)))
+
+
+def test_argument_errors():
+    r, a, n = rasters(8, 8, False)
+
+    def raises(fn):
+        with pytest.raises(hrt.HrtError) as e:
+            fn()
+        assert e.value.status == hrt.ERR_INVALID_ARG
+
+    for it in (0, 6):
+        raises(lambda: hrt.debug_guided(r, a, n, it, 4.0))
+    for sigma in (0.0, -1.0, float("nan")):
+        raises(lambda: hrt.debug_guided(r, a, n, 3, sigma))
+    for bad in (-1.0, float("nan")):
+        for key in ("kn", "ka", "kz"):
+            raises(lambda: hrt.debug_guided(r, a, n, 3, 4.0, **{key: bad}))
+    L = hrt.load()
+    out = np.zeros_like(r)
+    args = (8, 8, 3, 4.0, 0.0, 0.0, 0.0)
+    assert L.hrt_debug_guided(0, None, a.ctypes.data, n.ctypes.data, *args, out.ctypes.data) == hrt.ERR_INVALID_ARG
+    assert L.hrt_debug_guided(0, r.ctypes.data, None, n.ctypes.data, *args, out.ctypes.data) == hrt.ERR_INVALID_ARG
+    assert L.hrt_debug_guided(0, r.ctypes.data, a.ctypes.data, None, *args, out.ctypes.data) == hrt.ERR_INVALID_ARG
+    assert L.hrt_debug_guided(0, r.ctypes.data, a.ctypes.data, n.ctypes.data, *args, None) == hrt.ERR_INVALID_ARG
+    assert L.hrt_debug_guided(0, r.ctypes.data, a.ctypes.data, n.ctypes.data, 0, 8, 3, 4.0, 0.0, 0.0, 0.0, out.ctypes.data) == hrt.ERR_INVALID_ARG
+    assert not out.any()
+    with pytest.raises(ValueError):
+        hrt.debug_guided(r, a[:4], n, 3, 4.0)
+
+
+def test_guided_params_layout_and_abi_version():
+    assert ctypes.sizeof(hrt.GuidedParams) == 20
+    assert [(nm, getattr(hrt.GuidedParams, nm).offset) for nm, _ in hrt.GuidedParams._fields_] == [
+        ("iterations", 0), ("sigma", 4), ("normal", 8), ("albedo", 12), ("depth", 16)]
+    assert hrt.ABI_VERSION == 6 and hrt.load().hrt_abi_version() == 6
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header = open(os.path.join(root, "include", "hrt", "hrt.h")).read()
+    assert "#define HRT_ABI_VERSION 6u" in header and "struct hrt_guided_params { /* 20 bytes */" in header
+    g = hrt.guided_params()
+    assert (g.iterations, g.sigma) == (3, 4.0)
+    assert (g.normal, g.albedo, g.depth) == tuple(F(hrt.GUIDED_DEFAULTS[k]) for k in ("normal", "albedo", "depth"))
+    g = hrt.guided_params(iterations=5, sigma=2.0, normal=0.0, depth=0.25)
+    assert (g.iterations, g.sigma, g.normal, g.albedo, g.depth) == (5, 2.0, 0.0, F(hrt.GUIDED_DEFAULTS["albedo"]), 0.25)
