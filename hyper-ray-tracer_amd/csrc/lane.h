@@ -98,9 +98,11 @@ struct KParams {
   uint32_t walk_pbase; /* walk_c16: byte offset of the payloads */
   uint32_t n_chunks;   /* chunks per pixel (host side and the lane simulator; the kernels read direct_out) */
   /* the camera segment's leaf lists (primary_list.h): one 16-B record per frame-aligned 8x8 pixel cell, cell
-   * (px >> 3, py >> 3) at [(py >> 3) * cells_x + (px >> 3)]; null: every ray walks the stream */
+   * (px >> 3, py >> 3) at [(py >> 3) * cells_x + (px >> 3)]; null: every ray walks the stream.  The cell's
+   * extension record (entries 8 .. 15) is in a second table behind the first, cells_x * cells_y records further on */
   const uint4* prim_lists;
-  uint32_t cells_x;
+  uint32_t cells_x;  /* the builder's (render.hip build_primary_lists) */
+  uint32_t cells_xy; /* the sphere kernel's: cells_x | cells_y << 16 (one kernel parameter for both counts) */
 };
 
 /* Sample-chunk size: spp <= cmin keeps one work item per pixel (the reference's sequential sum), larger

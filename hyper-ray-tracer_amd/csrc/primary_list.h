@@ -9,6 +9,13 @@
  * order; the sphere kernel then tests a camera ray against its cell's list instead of walking the hierarchy
  * (render_sphere.hip).
  *
+ * A list holds up to 16 leaves in two 16-B records of two tables: the cell's record (entries 0 .. 7, what
+ * build_cell fills) and its extension record (entries 8 .. 15, build_cell_wide).  A cell with more leaves than
+ * the capacity gets an overflow record and its rays walk the stream.  The builder walks the stream with the
+ * beam as a ray would, leaving by its skip link every subtree whose inner box the beam misses, so a cell costs
+ * a few dozen box tests, not one per leaf.  A launch builds the lists once per view (render.hip: the scene keeps
+ * them while the stream, the camera, the frame size and the capacity stay the same).
+ *
  * Soundness: a leaf is left out only if its box [C - E, C + E], inflated as lane.h box_ce inflates it and padded
  * for every f32 rounding between the camera and the slab comparison, misses a hull of all the cell's rays in
  * real arithmetic (f64 here, whose own rounding is 2^-29 of the smallest pad).  The hull only has to hold the
@@ -47,6 +54,7 @@ namespace plist {
 namespace G = hrt::gpu;
 
 constexpr uint32_t PL_CAP = 8;          /* entries of a record (8 x u16 = 16 B) */
+constexpr uint32_t PL_CAP_WIDE = 16;    /* entries of a list: a record and its extension record */
 constexpr uint32_t PL_UNUSED = 0xFFFFu; /* an unused entry */
 constexpr uint32_t PL_OVERFLOW = 0xFFFEu; /* entry 0 of an overflow record: the cell's rays take the walk */
 /* entries are node-part offsets / 16: the stream must end within 65 535 units, below the two codes */
@@ -147,32 +155,57 @@ HRT_HD bool leaf_in_beam(const Beam& B, const float4& c, const float4& e) {
 }
 
 /* The leaf list of cell (bx, by) over the walk stream `walk` (32-B node parts, 16 B between a part's halves,
- * laid out whole: layout.h), cap in [1, PL_CAP] entries.  Returns the number of leaves the beam meets (the
- * record is an overflow record when that exceeds cap).  The stream is read in pre-order through its own
- * links: an inner node's pass is its first child, a leaf's skip its successor. */
-HRT_HD uint32_t build_cell(const lane::KParams& P, uint32_t bx, uint32_t by, uint32_t cap, Record& rec) {
+ * laid out whole: layout.h), cap in [1, PL_CAP_WIDE] entries: entries 0 .. 7 in `rec`, entries 8 .. 15 in the
+ * extension record `ext` (all unused for a list of at most 8).  Returns the number of leaves the builder meets
+ * (more than cap: `rec` is an overflow record, `ext` unused).  A full first record (e[7] used) is all that tells
+ * a reader that the extension may hold more.
+ * The stream is walked as a ray walks it, with the beam in the ray's place: a node part, inner or leaf, whose
+ * padded inflated box the beam misses is left by its skip link, an inner node the beam meets by its pass link
+ * (its first child), a leaf by its skip (its successor).  Pruning by inner nodes is sound by the argument of the
+ * header: the walk hands a leaf to walk_leaf_test only after its ray passed every ancestor's inflated box, and a
+ * beam that misses an ancestor's padded inflated box holds no such ray. */
+HRT_HD uint32_t build_cell_wide(const lane::KParams& P, uint32_t bx, uint32_t by, uint32_t cap, Record& rec, Record& ext) {
   const Beam B = cell_beam(P, bx, by);
-  for (uint32_t j = 0; j < PL_CAP; j++) rec.e[j] = (uint16_t)PL_UNUSED;
+  for (uint32_t j = 0; j < PL_CAP; j++) rec.e[j] = ext.e[j] = (uint16_t)PL_UNUSED;
   uint32_t n = 0;
+  /* the builder's watchdog: a walk visits a node part (32 B) at most once, so more steps than the stream has
+   * parts mean links that cycle (a corrupt stream: inner skip links are followed here).  The cell then gets an
+   * overflow record and its rays take the stream walk, whose own watchdog reports the scene. */
+  uint32_t steps_left = P.walk_end / 32u + 1u;
   for (uint32_t off = 0; off < P.walk_end;) {
+    if (steps_left-- == 0u) {
+      n = PL_CAP_WIDE + 1u;
+      break;
+    }
     const float4 a = *reinterpret_cast<const float4*>(P.walk + off);
     const float4 b = *reinterpret_cast<const float4*>(P.walk + off + 16u);
     const uint32_t pass = f2u(b.w);
+    if (!leaf_in_beam(B, a, b)) {
+      off = f2u(a.w);
+      continue;
+    }
     if (!lane::walk_pending(pass)) {
       off = pass;
       continue;
     }
-    if (leaf_in_beam(B, a, b)) {
-      if (n < cap) rec.e[n] = (uint16_t)(off >> 4);
-      n++;
+    if (n < cap) {
+      if (n < PL_CAP) rec.e[n] = (uint16_t)(off >> 4);
+      else ext.e[n - PL_CAP] = (uint16_t)(off >> 4);
     }
+    n++;
     off = f2u(a.w);
   }
   if (n > cap) {
-    for (uint32_t j = 0; j < PL_CAP; j++) rec.e[j] = (uint16_t)PL_UNUSED;
+    for (uint32_t j = 0; j < PL_CAP; j++) rec.e[j] = ext.e[j] = (uint16_t)PL_UNUSED;
     rec.e[0] = (uint16_t)PL_OVERFLOW;
   }
   return n;
+}
+
+/* The list of at most cap <= PL_CAP entries: build_cell_wide's first record. */
+HRT_HD uint32_t build_cell(const lane::KParams& P, uint32_t bx, uint32_t by, uint32_t cap, Record& rec) {
+  Record ext;
+  return build_cell_wide(P, bx, by, cap < PL_CAP ? cap : PL_CAP, rec, ext);
 }
 
 }  // namespace plist

@@ -758,6 +758,9 @@ hrt_status device_upload(hrt_scene* s, int device) {
       sl.used = false;
       sl.tiles_cap = 0;
     }
+    hipEvent_t lev;
+    hip_check(hipEventCreateWithFlags(&lev, hipEventDisableTiming), "hipEventCreate");
+    s->view_lists.event = lev;
   });
 }
 
@@ -777,6 +780,11 @@ void device_release(hrt_scene* s) {
     if (sl.h_tiles) (void)hipHostFree(sl.h_tiles);
     sl = hrt_scene::Slot();
   }
+  /* the view's leaf lists go with the stream they were built over (every launch that read them has ended: the
+   * slots' events above) */
+  if (s->view_lists.event) (void)hipEventDestroy((hipEvent_t)s->view_lists.event);
+  if (s->view_lists.d_lists) (void)hipFree(s->view_lists.d_lists);
+  s->view_lists = hrt_scene::ViewLists();
   delete static_cast<std::mutex*>(s->slot_mutex);
   s->slot_mutex = nullptr;
   if (OutPool* pool = static_cast<OutPool*>(s->out_pool)) {
@@ -799,6 +807,7 @@ namespace {
  * stream in LDS first (it is one the sphere kernel stages whole), so the builder's walk through the links reads
  * LDS, not one dependent global load per node. */
 constexpr int LISTS_BLOCK = 256;
+constexpr uint32_t LISTS_POSTPONE = 56; /* HRT_POSTPONE's default for a launch that reads lists (render_launch) */
 __global__ __launch_bounds__(LISTS_BLOCK) void build_primary_lists(KParams P, uint32_t cap, uint32_t n_cells, uint4* out) {
   extern __shared__ float4 lds_stream[];
   const float4* g = reinterpret_cast<const float4*>(P.walk);
@@ -808,23 +817,40 @@ __global__ __launch_bounds__(LISTS_BLOCK) void build_primary_lists(KParams P, ui
   if (c >= n_cells) return;
   KParams Q = P;
   Q.walk = reinterpret_cast<const uint8_t*>(lds_stream);
-  plist::Record rec;
-  plist::build_cell(Q, c % P.cells_x, c / P.cells_x, cap, rec);
+  plist::Record rec, ext;
+  plist::build_cell_wide(Q, c % P.cells_x, c / P.cells_x, cap, rec, ext);
   out[c] = *reinterpret_cast<const uint4*>(&rec);
+  out[n_cells + c] = *reinterpret_cast<const uint4*>(&ext);
 }
 
 /* The capacity of the leaf lists a launch builds, 0 for none.  Lists are built for the sphere kernel's plain
  * instantiation alone: a sphere stream staged whole in LDS with 32-B node parts under exact culling (not HEAVY,
  * hybrid, split, 16-B parts or the packet walk), short enough for the records' 16-bit entries.
- * HRT_PRIMARY_LISTS (A/B knob): "0" builds none, 1..8 is the capacity (cells with more leaves walk the stream). */
+ * HRT_PRIMARY_LISTS (A/B knob): "0" builds none, 1..16 is the capacity (cells with more leaves walk the stream;
+ * above 8 the extension records are in use); unset: 16. */
 uint32_t primary_list_cap(const hrt_scene* s, const Plan& pl) {
   if (pl.full || pl.fast || pl.general || pl.gwalk || pl.heavy || pl.sphere_packet || !pl.lds || pl.cull != G::CULL_EXACT)
     return 0;
   if (s->w_general || s->w_hot || s->w_c16 || s->w_half != 16u || s->w_end == 0 || s->w_end > plist::PL_MAX_WALK_BYTES) return 0;
   const char* e = knob_env("HRT_PRIMARY_LISTS");
-  if (!e) return plist::PL_CAP;
+  if (!e) return plist::PL_CAP_WIDE;
   const long x = strtol(e, nullptr, 10);
-  return x >= 1 && x <= (long)plist::PL_CAP ? (uint32_t)x : 0u;
+  return x >= 1 && x <= (long)plist::PL_CAP_WIDE ? (uint32_t)x : 0u;
+}
+
+/* What a cell's list depends on besides the committed stream and the device (both fixed between two commits):
+ * every camera field the beam reads (primary_list.h cell_beam), the frame size and the capacity. */
+void lists_key(const KParams& kp, uint32_t cap, uint32_t out[hrt_scene::LISTS_KEY_WORDS]) {
+  const Vec3 v[6] = {kp.cam_origin, kp.cam_llc, kp.cam_h, kp.cam_v, kp.cam_u, kp.cam_vv};
+  for (int k = 0; k < 6; k++) {
+    out[3 * k] = f2u(v[k].x);
+    out[3 * k + 1] = f2u(v[k].y);
+    out[3 * k + 2] = f2u(v[k].z);
+  }
+  out[18] = f2u(kp.lens_radius);
+  out[19] = kp.W;
+  out[20] = kp.H;
+  out[21] = cap;
 }
 
 void launch_primary_lists(const hrt_scene* s, const KParams& kp, uint32_t cap, uint32_t n_cells, void* d_lists, hipStream_t stream) {
@@ -936,9 +962,11 @@ void hrt::render_launch(hrt_scene* s, const hrt_camera* cam, const hrt_render_pa
   size_t tiles_bytes = n_tiles * sizeof(G::TileDev);
   const size_t partial_bytes = n_chunks > 1 || raw ? (size_t)n_chunks * outp * sizeof(float4) : 0;
   const Plan pl = plan(s, cam, p->flags);
-  const uint32_t list_cap = primary_list_cap(s, pl);
+  /* the kernel reads the frame's cell counts as two 16-bit fields (lane.h KParams cells_xy) */
+  const bool cells_fit = plist::cells_x(p->width) <= 0xFFFFu && plist::cells_y(p->height) <= 0xFFFFu;
+  const uint32_t list_cap = cells_fit ? primary_list_cap(s, pl) : 0u;
   const uint32_t n_cells = plist::cells_x(p->width) * plist::cells_y(p->height);
-  const size_t lists_bytes = list_cap ? (size_t)n_cells * sizeof(plist::Record) : 0;
+  const size_t lists_bytes = list_cap ? 2u * (size_t)n_cells * sizeof(plist::Record) : 0; /* records, extension records */
   auto grow = [&](hrt_scene::Slot& g, bool partial) {
     if (lists_bytes > g.lists_cap) { /* sized at the slot's first use, with its tile table: no timed step allocates */
       if (g.d_lists) hip_check(hipFree(g.d_lists), "hipFree(lists)");
@@ -982,10 +1010,65 @@ void hrt::render_launch(hrt_scene* s, const hrt_camera* cam, const hrt_render_pa
                            stream), "hipMemcpyAsync(tiles)");
   KParams kp = scene_params(s, cam, p, pl);
   kp.cells_x = plist::cells_x(p->width);
+  kp.cells_xy = plist::cells_x(p->width) | plist::cells_y(p->height) << 16;
+  sl.view_lists = false;
   if (list_cap) {
-    launch_primary_lists(s, kp, list_cap, n_cells, sl.d_lists, stream);
-    kp.prim_lists = (const uint4*)sl.d_lists;
+    /* with lists the camera segments no longer enter the walk loop, and the loop pays to wait for more finished
+     * lanes before it leaves to shade: HRT_POSTPONE 44 / 48 / 52 / 56 / 60 = 16 556 / 16 972 / 17 307 / 17 455 /
+     * 17 109 Mrays/s on C2 (profiles/primary_lists16_ab.jsonl); without lists (scene_params) 52 stays */
+    kp.postpone = env_knob("HRT_POSTPONE", LISTS_POSTPONE);
+    /* The lists are the view's, not the launch's: built once into the scene's buffer and read by every launch
+     * with the same key, on this stream behind the build or on another behind the build's event.  Another key
+     * rebuilds them in place when no launch in flight reads them (the slots' events say so); otherwise this
+     * launch builds into its slot's own buffer, as every launch did before, and leaves the scene's alone. */
+    hrt_scene::ViewLists& vl = s->view_lists;
+    uint32_t key[hrt_scene::LISTS_KEY_WORDS];
+    lists_key(kp, list_cap, key);
+    void* lists = sl.d_lists;
+    if (vl.valid && memcmp(vl.key, key, sizeof(key)) == 0) {
+      hip_check(hipStreamWaitEvent(stream, (hipEvent_t)vl.event, 0), "hipStreamWaitEvent(lists)"); /* the builder's own stream too */
+      lists = vl.d_lists;
+      sl.view_lists = true;
+    } else {
+      bool read = false; /* a launch in flight reads the scene's lists */
+      for (auto& other : s->slots)
+        read = read || (&other != &sl && other.used && other.view_lists && hipEventQuery((hipEvent_t)other.event) != hipSuccess);
+      if (!read && lists_bytes > vl.cap) { /* sized with the slots, at the first launch of a frame size */
+        vl.valid = false;
+        if (vl.d_lists) hip_check(hipFree(vl.d_lists), "hipFree(view lists)");
+        vl.d_lists = nullptr;
+        vl.cap = 0;
+        hip_check(hipMalloc(&vl.d_lists, lists_bytes), "hipMalloc(view lists)");
+        vl.cap = lists_bytes;
+      }
+      if (!read && vl.cap >= lists_bytes) {
+        vl.valid = false;
+        launch_primary_lists(s, kp, list_cap, n_cells, vl.d_lists, stream);
+        hip_check(hipEventRecord((hipEvent_t)vl.event, stream), "hipEventRecord(lists)");
+        memcpy(vl.key, key, sizeof(key));
+        vl.valid = true;
+        lists = vl.d_lists;
+        sl.view_lists = true;
+      } else {
+        launch_primary_lists(s, kp, list_cap, n_cells, sl.d_lists, stream);
+      }
+    }
+    kp.prim_lists = (const uint4*)lists;
   }
+  /* A launch that fails from here on records no slot event, so nothing would say that its build or its kernel
+   * may still be using the scene's lists: wait for the stream and drop the lists instead (error path only). */
+  struct ListsGuard {
+    hrt_scene::Slot& sl;
+    hrt_scene::ViewLists& vl;
+    hipStream_t stream;
+    bool armed;
+    ~ListsGuard() {
+      if (!armed || !sl.view_lists) return;
+      (void)hipStreamSynchronize(stream);
+      sl.view_lists = false;
+      vl.valid = false; /* also when this launch only read them: the next launch rebuilds, which is always right */
+    }
+  } lists_guard{sl, s->view_lists, stream, true};
   kp.tiles = (const G::TileDev*)((uint8_t*)scratch + SLOT_HDR);
   kp.n_tiles = n_tiles;
   kp.total_work = (uint32_t)(pad * n_chunks);
@@ -1035,6 +1118,7 @@ void hrt::render_launch(hrt_scene* s, const hrt_camera* cam, const hrt_render_pa
   unsigned long long* h = (unsigned long long*)sl.h_tiles;
   hip_check(hipMemcpyAsync(h, (uint8_t*)scratch + 8, 136, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(stats)");
   hip_check(hipEventRecord((hipEvent_t)sl.event, stream), "hipEventRecord(slot)");
+  lists_guard.armed = false;
   sl.used = true;
   if (stats) {
     hip_check(hipEventSynchronize((hipEvent_t)sl.event), "hipEventSynchronize(stats)");
@@ -1099,6 +1183,8 @@ hrt_status hrt_debug_poke_blob(hrt_scene* s, uint64_t offset, const void* data, 
     DeviceGuard dg(s->device);
     hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
     hip_check(hipMemcpy((uint8_t*)s->d_blob + offset, data, n, hipMemcpyHostToDevice), "hipMemcpy(poke)");
+    std::lock_guard<std::mutex> lock(*static_cast<std::mutex*>(s->slot_mutex));
+    s->view_lists.valid = false; /* the lists were built over the blob's walk stream */
   });
 }
 

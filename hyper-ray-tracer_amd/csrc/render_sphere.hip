@@ -155,7 +155,7 @@ void render_basic_kernel(KParams P) {
     if (has_item && !walking) {
       if constexpr (LISTS) {
         if (P.prim_lists) {
-          rec = P.prim_lists[(it.pxy >> 19) * P.cells_x + ((it.pxy & 0xFFFFu) >> 3)];
+          rec = P.prim_lists[(it.pxy >> 19) * (P.cells_xy & 0xFFFFu) + ((it.pxy & 0xFFFFu) >> 3)];
           fresh = true;
         }
       }
@@ -193,21 +193,35 @@ void render_basic_kernel(KParams P) {
     if constexpr (LISTS) {
       const bool listed = fresh && ps.depth_left != 0 && (rec.x & 0xFFFFu) != plist::PL_OVERFLOW && !nan_mode(r);
       if (__ballot(listed)) {
-        const uint32_t ew[4] = {rec.x, rec.y, rec.z, rec.w};
+        /* the eight rounds run at most twice: on the cell's record, then, for the lanes whose record is full
+         * (e[7] used: more may follow), on its extension record, loaded only then (a dependent load in the few
+         * cells with more than 8 leaves).  A wave's lanes may belong to two cells, so the decision is per lane */
+        bool more = listed;
+        if (listed) node = end; /* the rounds below finish the lane's walk (they do not read `node`) */
+#pragma unroll 1
+        for (int trip = 0;; trip++) {
+          const uint32_t ew[4] = {rec.x, rec.y, rec.z, rec.w};
 #pragma unroll
-        for (int j = 0; j < (int)plist::PL_CAP; j++) {
-          const uint32_t e = (ew[j >> 1] >> (16 * (j & 1))) & 0xFFFFu;
-          const bool act = listed && e != plist::PL_UNUSED;
-          if (!__ballot(act)) break;
-          bool pass = false;
-          uint32_t leaf = 0u;
-          if (act) {
-            if constexpr (COUNT) cn.steps++;
-            pass = list_step<COUNT, WMEM>(ws, e << 4, r, tmin_c, closest, cn, leaf);
+          for (int j = 0; j < (int)plist::PL_CAP; j++) {
+            const uint32_t e = (ew[j >> 1] >> (16 * (j & 1))) & 0xFFFFu;
+            const bool act = more && e != plist::PL_UNUSED;
+            if (!__ballot(act)) break;
+            bool pass = false;
+            uint32_t leaf = 0u;
+            if (act) {
+              if constexpr (COUNT) cn.steps++;
+              pass = list_step<COUNT, WMEM>(ws, e << 4, r, tmin_c, closest, cn, leaf);
+            }
+            if (pass) walk_leaf_test<COUNT, WMEM>(P, ws, leaf, r, closest, winner, cn);
           }
-          if (pass) walk_leaf_test<COUNT, WMEM>(P, ws, leaf, r, closest, winner, cn);
+          more = more && trip == 0 && (rec.w >> 16) != plist::PL_UNUSED;
+          if (!__ballot(more)) break;
+          /* the extension table follows the cells_x x cells_y records; both counts in ONE parameter: a second one
+           * kept live across the loop took the 65th spilled SGPR, and with it a VGPR from the path state */
+          if (more)
+            rec = P.prim_lists[(P.cells_xy & 0xFFFFu) * (P.cells_xy >> 16) + (it.pxy >> 19) * (P.cells_xy & 0xFFFFu) +
+                               ((it.pxy & 0xFFFFu) >> 3)];
         }
-        if (listed) node = end;
         short_pass = !short_prev;
       }
     }

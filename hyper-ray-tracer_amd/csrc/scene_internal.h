@@ -166,12 +166,26 @@ struct hrt_scene {
     void* event = nullptr; /* hipEvent_t */
     void* d_partial = nullptr; /* sample-chunk sums [pixels][n_chunks] */
     size_t partial_cap = 0;
-    void* d_lists = nullptr; /* the camera segment's per-cell leaf lists (primary_list.h), 16 B per 8x8 pixel cell */
+    void* d_lists = nullptr; /* leaf lists of the slot's own (primary_list.h: two tables of 16 B per 8x8 pixel cell),
+                                built by a launch that may not touch the scene's (ViewLists) */
     size_t lists_cap = 0;
+    bool view_lists = false; /* the slot's last launch reads the scene's lists */
     bool used = false;
   };
   static constexpr int N_SLOTS = 4;
   Slot slots[N_SLOTS];
+  /* The camera segment's leaf lists of the last view rendered, built once and read by every later launch with the
+   * same key (render.hip lists_key) on any stream: each of them waits for `event` on its own stream.
+   * A launch with another key rebuilds them when no launch in flight reads them, and builds into its
+   * slot's own buffer otherwise.  Dropped with the device state (device_release: commit, destruction). */
+  static constexpr int LISTS_KEY_WORDS = 22;
+  struct ViewLists {
+    void* d_lists = nullptr;
+    size_t cap = 0;
+    bool valid = false;
+    uint32_t key[LISTS_KEY_WORDS] = {};
+    void* event = nullptr; /* hipEvent_t recorded behind the build */
+  } view_lists;
   unsigned next_slot = 0;
   void* slot_mutex = nullptr; /* std::mutex*, owned by render.hip */
   void* out_pool = nullptr;   /* hrt_render's reusable device output buffers (render.hip OutPool) */
