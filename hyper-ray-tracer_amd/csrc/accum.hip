@@ -12,6 +12,7 @@
 
 #include "accum.h"
 #include "accum_ledger.h"
+#include "accum_snapshot.h"
 #include "feature_pass.h"
 #include "filter.h"
 #include "render_host.h"
@@ -113,6 +114,32 @@ __global__ __launch_bounds__(256) void accum_merge(float4* __restrict__ dst, con
 __global__ __launch_bounds__(256) void accum_merge_m2(float* __restrict__ dst, const float* __restrict__ src, size_t n) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
     dst[i] = accum::add_moment(dst[i], src[i]);
+}
+
+/* One selected tile of hrt_accum_merge_tiles: its pixels [off, off + n) of the packed order are pixels [sel, sel + n)
+ * of the launch, which runs over the selected tiles' pixels alone. */
+struct alignas(16) MergeTile {
+  uint32_t off, n, sel, pad;
+};
+/* dst += src (and dst.m2 += src.m2) on the selected tiles; a pixel of the launch finds its tile as mapped_pixel does:
+ * the last tile whose sel <= i.  No other pixel is read or written. */
+template <bool MOMENTS>
+__global__ __launch_bounds__(256) void accum_merge_tiles(float4* __restrict__ dst, const float4* __restrict__ src,
+                                                         float* __restrict__ dst_m2, const float* __restrict__ src_m2,
+                                                         const MergeTile* __restrict__ tiles, uint32_t n_tiles, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    uint32_t lo = 0, hi = n_tiles;
+    while (hi - lo > 1u) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (tiles[mid].sel <= i) lo = mid;
+      else hi = mid;
+    }
+    const size_t d = (size_t)tiles[lo].off + (i - tiles[lo].sel);
+    const float4 a = dst[d], b = src[d];
+    const Vec3 sum = accum::add_pass(v3(a.x, a.y, a.z), v3(b.x, b.y, b.z));
+    dst[d] = make_float4(sum.x, sum.y, sum.z, 0.0f);
+    if constexpr (MOMENTS) dst_m2[d] = accum::add_moment(dst_m2[d], src_m2[d]);
+  }
 }
 
 /* One tile of an accumulator as accum_noise and accum_resolve_tiles see it: its pixels [off, off + n) of the packed
@@ -284,6 +311,9 @@ struct hrt_accum {
   uint32_t feat_blocks = 0, feat_log_bw = 0;
   /* the guided resolve's two mean feature rasters over the planes' bounding box, made by the first guided resolve */
   float4* d_gplane[2] = {nullptr, nullptr};
+  /* hrt_accum_merge_tiles' table of the selected tiles, made by the first such merge, and its host copy */
+  MergeTile* d_mtiles = nullptr;
+  std::vector<MergeTile> h_mtiles;
 };
 
 namespace {
@@ -540,6 +570,61 @@ void accum_add(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, 
   a->ledger.record(r, pass_chunks(a->scene, p), idx, n);
 }
 
+/* hrt_accum_merge's preconditions beyond usable: the same device, image, tiles and planes on both sides */
+void merge_compatible(const hrt_accum* dst, const hrt_accum* src, const char* who) {
+  const std::string w(who);
+  if ((dst->d_m2 != nullptr) != (src->d_m2 != nullptr))
+    throw HipError{HRT_ERR_INVALID_ARG, w + ": one accumulator keeps a noise plane (HRT_ACCUM_NOISE), the other none"};
+  if (dst->device != src->device || dst->width != src->width || dst->height != src->height || dst->tiles.size() != src->tiles.size() ||
+      memcmp(dst->tiles.data(), src->tiles.data(), dst->tiles.size() * sizeof(hrt_tile)) != 0)
+    throw HipError{HRT_ERR_INVALID_ARG, w + ": the accumulators differ in device, image size or tiles"};
+  if ((dst->d_fa != nullptr) != (src->d_fa != nullptr))
+    throw HipError{HRT_ERR_INVALID_ARG, w + ": one accumulator keeps feature planes (HRT_ACCUM_FEATURES), the other none"};
+}
+
+/* ---- snapshots (accum_snapshot.h is the codec; here: the accumulator's state into and out of its State) ---- */
+uint32_t accum_flags(const hrt_accum* a) { return (a->d_m2 ? HRT_ACCUM_NOISE : 0u) | (a->d_fa ? HRT_ACCUM_FEATURES : 0u); }
+/* the identity's 128 bytes as hrt.h lays them out; width and height are the accumulator's */
+void identity_bytes(const FrameIdentity& id, uint8_t* out) {
+  static_assert(sizeof(hrt_camera) == 96, "the snapshot layout holds 96 camera bytes");
+  memcpy(out, &id.cam, 96);
+  snapshot::put32(out + 96, id.max_depth);
+  snapshot::put32(out + 100, id.flags);
+  memcpy(out + 104, &id.t_min, 4);
+  memcpy(out + 108, id.background, 12);
+  snapshot::put64(out + 120, id.seed);
+}
+FrameIdentity identity_from(const uint8_t* in, uint32_t width, uint32_t height) {
+  FrameIdentity id;
+  memset(&id, 0, sizeof(id));
+  memcpy(&id.cam, in, 96);
+  id.width = width;
+  id.height = height;
+  id.max_depth = snapshot::get32(in + 96);
+  id.flags = snapshot::get32(in + 100);
+  memcpy(&id.t_min, in + 104, 4);
+  memcpy(id.background, in + 108, 12);
+  id.seed = snapshot::get64(in + 120);
+  return id;
+}
+snapshot::State snapshot_state(const hrt_accum* a) {
+  snapshot::State s;
+  s.flags = accum_flags(a);
+  s.width = a->width;
+  s.height = a->height;
+  for (const hrt_tile& t : a->tiles) s.tiles.push_back(snapshot::Tile{t.x, t.y, t.w, t.h});
+  s.has_identity = a->has_identity;
+  if (a->has_identity) identity_bytes(a->identity, s.identity);
+  s.records = a->ledger.records();
+  if (a->d_fa) s.f_ranges = *a->f_ledger.ranges(); /* every feature pass covers every tile: always the shared record */
+  snapshot::layout(s);
+  return s;
+}
+void snapshot_decode(const void* blob, uint64_t size, snapshot::State& s, const char* who) {
+  const snapshot::Error e = snapshot::decode(blob, size, s);
+  if (e != snapshot::OK) throw HipError{HRT_ERR_INVALID_ARG, std::string(who) + ": malformed snapshot: " + snapshot::error_text(e)};
+}
+
 }  // namespace
 
 extern "C" {
@@ -628,7 +713,7 @@ void hrt_accum_destroy(hrt_accum* a) {
   for (float4* plane : a->d_fplane)
     if (plane) (void)hipFree(plane);
   if (a->d_ftiles) (void)hipFree(a->d_ftiles);
-  for (void* p : {(void*)a->d_fa, (void*)a->d_fn, (void*)a->d_feat_tiles, (void*)a->d_gplane[0], (void*)a->d_gplane[1]})
+  for (void* p : {(void*)a->d_fa, (void*)a->d_fn, (void*)a->d_feat_tiles, (void*)a->d_gplane[0], (void*)a->d_gplane[1], (void*)a->d_mtiles})
     if (p) (void)hipFree(p);
   if (prev >= 0) (void)hipSetDevice(prev);
   delete a;
@@ -950,6 +1035,139 @@ hrt_status hrt_accum_upload(hrt_accum* a, const hrt_camera* cam, const hrt_rende
     a->identity = id;
     a->has_identity = true;
     a->ledger = held;
+  });
+}
+
+hrt_status hrt_accum_merge_tiles(hrt_accum* dst, const hrt_accum* src, void* stream) {
+  return hguard([&] {
+    if (!dst || !src || dst == src) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_merge_tiles: null argument, or an accumulator into itself"};
+    accum_usable(dst);
+    accum_usable(src);
+    merge_compatible(dst, src, "hrt_accum_merge_tiles");
+    const bool feats = src->d_fa && !src->f_ledger.empty();
+    if (src->ledger.empty() && !feats) return;
+    check_identity(dst, src->identity);
+    if (!dst->ledger.may_merge(src->ledger))
+      throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_merge_tiles: a tile's sample ranges overlap samples the accumulator's tile holds"};
+    if (feats)
+      for (const SampleRange& r : *src->f_ledger.ranges()) check_range(dst->f_ledger.may_add(r));
+    DeviceGuard dg(dst->device);
+    /* the tiles for which src holds samples, and the launch's pixels */
+    const uint32_t nt = (uint32_t)dst->tiles.size();
+    std::vector<MergeTile> sel;
+    uint64_t n_sel = 0;
+    for (uint32_t t = 0; t < nt; t++) {
+      if (src->ledger.samples(t) == 0) continue;
+      const uint32_t n = dst->tiles[t].w * dst->tiles[t].h;
+      sel.push_back(MergeTile{dst->tile_off[t], n, (uint32_t)n_sel, 0u});
+      n_sel += n;
+    }
+    if (!sel.empty() && !dst->d_mtiles) hip_check(hipMalloc((void**)&dst->d_mtiles, nt * sizeof(MergeTile)), "hipMalloc(merge tiles)");
+    if (feats) {
+      features::launch_feature_merge(dst->d_fa, dst->d_fn, src->d_fa, src->d_fn, dst->n_px, stream);
+      dst->f_ledger.merge(src->f_ledger);
+      dst->identity = src->identity;
+      dst->has_identity = true;
+    }
+    if (sel.empty()) return;
+    dst->h_mtiles.swap(sel); /* stays alive with the accumulator, as h_ntiles does */
+    const uint32_t n_tiles = (uint32_t)dst->h_mtiles.size();
+    hip_check(hipMemcpyAsync(dst->d_mtiles, dst->h_mtiles.data(), n_tiles * sizeof(MergeTile), hipMemcpyHostToDevice, (hipStream_t)stream),
+              "hipMemcpyAsync(merge tiles)");
+    if (dst->d_m2)
+      hipLaunchKernelGGL((accum_merge_tiles<true>), dim3(stream_blocks(n_sel)), dim3(256), 0, (hipStream_t)stream, dst->d_acc,
+                         (const float4*)src->d_acc, dst->d_m2, (const float*)src->d_m2, (const MergeTile*)dst->d_mtiles, n_tiles, (size_t)n_sel);
+    else
+      hipLaunchKernelGGL((accum_merge_tiles<false>), dim3(stream_blocks(n_sel)), dim3(256), 0, (hipStream_t)stream, dst->d_acc,
+                         (const float4*)src->d_acc, (float*)nullptr, (const float*)nullptr, (const MergeTile*)dst->d_mtiles, n_tiles,
+                         (size_t)n_sel);
+    hip_check(hipGetLastError(), "accum_merge_tiles launch");
+    dst->ledger.merge_tiles(src->ledger);
+    dst->identity = src->identity;
+    dst->has_identity = true;
+  });
+}
+
+hrt_status hrt_accum_snapshot(hrt_accum* a, void* out, uint64_t cap, uint64_t* size) {
+  return hguard([&] {
+    if (!a || !size) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_snapshot: null argument"};
+    accum_usable(a);
+    const snapshot::State s = snapshot_state(a);
+    *size = s.bytes;
+    if (!out) return;
+    if (cap < s.bytes) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_snapshot: the buffer is smaller than the snapshot"};
+    uint8_t* b = static_cast<uint8_t*>(out);
+    DeviceGuard dg(a->device);
+    hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    snapshot::encode_head(s, b);
+    hip_check(hipMemcpy(b + s.off_sums, a->d_acc, a->n_px * sizeof(float4), hipMemcpyDeviceToHost), "hipMemcpy(snapshot sums)");
+    if (a->d_m2) hip_check(hipMemcpy(b + s.off_m2, a->d_m2, a->n_px * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(snapshot m2)");
+    if (a->d_fa) {
+      hip_check(hipMemcpy(b + s.off_fa, a->d_fa, a->n_px * sizeof(float4), hipMemcpyDeviceToHost), "hipMemcpy(snapshot fa)");
+      hip_check(hipMemcpy(b + s.off_fn, a->d_fn, a->n_px * sizeof(float4), hipMemcpyDeviceToHost), "hipMemcpy(snapshot fn)");
+    }
+    snapshot::zero_pads(s, b);
+    snapshot::seal(s, b);
+  });
+}
+
+hrt_status hrt_accum_restore(hrt_accum* a, const void* blob, uint64_t size) {
+  return hguard([&] {
+    if (!a || !blob) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_restore: null argument"};
+    accum_usable(a);
+    if (!a->ledger.empty() || !a->f_ledger.empty())
+      throw HipError{HRT_ERR_STATE, "hrt_accum_restore: the accumulator holds samples: reset it first"};
+    snapshot::State s;
+    snapshot_decode(blob, size, s, "hrt_accum_restore");
+    if (s.flags != accum_flags(a) || s.width != a->width || s.height != a->height || s.tiles.size() != a->tiles.size())
+      throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_restore: the snapshot's flags, image size or tile count are not the accumulator's"};
+    for (size_t t = 0; t < s.tiles.size(); t++) {
+      const hrt_tile& T = a->tiles[t];
+      if (s.tiles[t].x != T.x || s.tiles[t].y != T.y || s.tiles[t].w != T.w || s.tiles[t].h != T.h)
+        throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_restore: the snapshot's tile list is not the accumulator's"};
+    }
+    const uint8_t* b = static_cast<const uint8_t*>(blob);
+    DeviceGuard dg(a->device);
+    hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize"); /* a reset's memsets, on whatever stream */
+    try {
+      hip_check(hipMemcpy(a->d_acc, b + s.off_sums, a->n_px * sizeof(float4), hipMemcpyHostToDevice), "hipMemcpy(restore sums)");
+      if (a->d_m2) hip_check(hipMemcpy(a->d_m2, b + s.off_m2, a->n_px * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(restore m2)");
+      if (a->d_fa) {
+        hip_check(hipMemcpy(a->d_fa, b + s.off_fa, a->n_px * sizeof(float4), hipMemcpyHostToDevice), "hipMemcpy(restore fa)");
+        hip_check(hipMemcpy(a->d_fn, b + s.off_fn, a->n_px * sizeof(float4), hipMemcpyHostToDevice), "hipMemcpy(restore fn)");
+      }
+      hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    } catch (...) {
+      a->invalid = true; /* some planes are the snapshot's, some not: only a reset makes it usable again */
+      throw;
+    }
+    a->ledger = AccumLedger(a->tiles.size(), std::move(s.records));
+    if (a->d_fa) {
+      std::vector<AccumLedger::Record> fr(1);
+      fr[0].ranges = std::move(s.f_ranges);
+      a->f_ledger = AccumLedger(a->tiles.size(), std::move(fr));
+    }
+    a->has_identity = s.has_identity;
+    if (s.has_identity) a->identity = identity_from(s.identity, a->width, a->height);
+  });
+}
+
+hrt_status hrt_accum_snapshot_info(const void* blob, uint64_t size, hrt_snapshot_info* info, hrt_tile* tiles, uint32_t cap) {
+  return hguard([&] {
+    if (!blob || !info) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_snapshot_info: null argument"};
+    snapshot::State s;
+    snapshot_decode(blob, size, s, "hrt_accum_snapshot_info");
+    memset(info, 0, sizeof(*info));
+    info->version = snapshot::VERSION;
+    info->flags = s.flags;
+    info->width = s.width;
+    info->height = s.height;
+    info->n_tiles = (uint32_t)s.tiles.size();
+    info->uniform = s.records.size() == 1 ? 1u : 0u;
+    info->n_pixels = s.n_px;
+    info->bytes = s.bytes;
+    if (tiles && cap >= s.tiles.size())
+      for (size_t t = 0; t < s.tiles.size(); t++) tiles[t] = hrt_tile{s.tiles[t].x, s.tiles[t].y, s.tiles[t].w, s.tiles[t].h};
   });
 }
 

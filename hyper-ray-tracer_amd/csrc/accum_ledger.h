@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <utility>
 #include <vector>
 
 namespace hrt {
@@ -42,7 +43,14 @@ inline uint64_t ranges_total(const std::vector<SampleRange>& have) {
 class AccumLedger {
  public:
   enum Refusal { ADDABLE = 0, BAD_RANGE, OVERLAP }; /* BAD_RANGE: empty, or its end past 2^32 */
+  /* what a tile (or, shared, every tile) holds */
+  struct Record {
+    std::vector<SampleRange> ranges;
+    uint64_t chunks = 0;
+  };
   explicit AccumLedger(size_t n_tiles = 0) : n_tiles_(n_tiles), held_(1) {}
+  /* from records() of a ledger of n_tiles tiles (a decoded snapshot): one record, or one per tile */
+  AccumLedger(size_t n_tiles, std::vector<Record> records) : n_tiles_(n_tiles), held_(std::move(records)) { rejoin(); }
 
   bool uniform() const { return held_.size() == 1; }
   bool empty() const { return uniform() && held_[0].ranges.empty(); } /* tiles that differ hold samples */
@@ -63,13 +71,7 @@ class AccumLedger {
   void record(const SampleRange& r, uint64_t k, const uint32_t* idx = nullptr, size_t n = 0) {
     if (uniform() && idx) held_.resize(n_tiles_, Held(held_[0])); /* the first subset pass: every tile starts from the shared record */
     for (size_t i = 0; i < (idx ? n : held_.size()); i++) add(held_[idx ? idx[i] : i], r, k);
-    for (const Held& h : held_) {
-      const auto &x = held_[0].ranges, &y = h.ranges;
-      if (h.chunks != held_[0].chunks || x.size() != y.size() ||
-          (!x.empty() && memcmp(x.data(), y.data(), x.size() * sizeof(SampleRange)) != 0))
-        return;
-    }
-    held_.resize(1); /* every tile holds the same passes (again, e.g. the pass went to all of them): one record */
+    rejoin();
   }
   /* the ranges and chunks of src, which may_add() allowed one by one; both uniform() */
   void merge(const AccumLedger& src) {
@@ -78,11 +80,41 @@ class AccumLedger {
   }
   void clear() { held_.assign(1, Held()); }
 
+  /* the records as held: one while uniform(), else one per tile (the snapshot codec writes them as they are) */
+  const std::vector<Record>& records() const { return held_; }
+  /* may src (of the same tiles) be merged tile by tile: for every tile, src's ranges disjoint from this one's? */
+  bool may_merge(const AccumLedger& src) const {
+    for (size_t t = 0; t < n_tiles_; t++)
+      for (const SampleRange& r : src.of(t).ranges)
+        if (ranges_overlap(of(t).ranges, r)) return false;
+    return true;
+  }
+  /* every tile for which src holds samples takes src's ranges and chunks (may_merge() allowed it); the others stay as
+   * they are.  Two uniform() ledgers: merge(). */
+  void merge_tiles(const AccumLedger& src) {
+    if (uniform() && src.uniform()) return merge(src);
+    if (uniform()) held_.resize(n_tiles_, Held(held_[0]));
+    for (size_t t = 0; t < n_tiles_; t++) {
+      const Held& s = src.of(t);
+      if (s.ranges.empty()) continue;
+      for (const SampleRange& r : s.ranges) add(held_[t], r, 0);
+      held_[t].chunks += s.chunks;
+    }
+    rejoin();
+  }
+
  private:
-  struct Held {
-    std::vector<SampleRange> ranges;
-    uint64_t chunks = 0;
-  };
+  using Held = Record;
+  /* one record again once every tile holds the same passes (e.g. the pass went to all of them) */
+  void rejoin() {
+    for (const Held& h : held_) {
+      const auto &x = held_[0].ranges, &y = h.ranges;
+      if (h.chunks != held_[0].chunks || x.size() != y.size() ||
+          (!x.empty() && memcmp(x.data(), y.data(), x.size() * sizeof(SampleRange)) != 0))
+        return;
+    }
+    held_.resize(1);
+  }
   static void add(Held& h, const SampleRange& r, uint64_t k) {
     ranges_insert(h.ranges, r);
     h.chunks += k;

@@ -160,6 +160,12 @@ class GuidedParams(ctypes.Structure):
                 ("albedo", ctypes.c_float), ("depth", ctypes.c_float)]
 
 
+class SnapshotInfo(ctypes.Structure):
+    """hrt_snapshot_info: what an accumulator must be created with to take a snapshot blob."""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("version", "flags", "width", "height", "n_tiles", "uniform")] + \
+        [("n_pixels", ctypes.c_uint64), ("bytes", ctypes.c_uint64)]
+
+
 class SceneOptions(ctypes.Structure):
     """hrt_scene_options: the explicit configuration that can change an image's bits (all-zero = default)."""
     _fields_ = [(n, ctypes.c_uint32) for n in ("bvh_ties", "walk_tree", "chunk_min", "chunk_max", "chunk_uniform")]
@@ -175,7 +181,8 @@ OPTIONAL = {"hrt_abi_version", "hrt_last_launch", "hrt_debug_box_test", "hrt_sce
             "hrt_debug_accum_moments",
             "hrt_accum_resolve_filtered", "hrt_accum_resolve_filtered_host", "hrt_debug_filter",
         "hrt_accum_add_features", "hrt_accum_feature_samples", "hrt_accum_features", "hrt_accum_features_host",
-            "hrt_accum_resolve_guided", "hrt_accum_resolve_guided_host", "hrt_debug_guided", "hrt_debug_accum_features"}
+            "hrt_accum_resolve_guided", "hrt_accum_resolve_guided_host", "hrt_debug_guided", "hrt_debug_accum_features",
+            "hrt_accum_snapshot", "hrt_accum_restore", "hrt_accum_snapshot_info", "hrt_accum_merge_tiles"}
 HRT_LIB_OVERRIDE = bool(os.environ.get("HRT_LIB"))
 
 # Every entry point of include/hrt/hrt.h (tests/test_abi.py checks the header against this list).
@@ -198,6 +205,7 @@ EXPORTS = [
     "hrt_accum_resolve_filtered", "hrt_accum_resolve_filtered_host", "hrt_debug_filter",
     "hrt_accum_add_features", "hrt_accum_feature_samples", "hrt_accum_features", "hrt_accum_features_host",
     "hrt_accum_resolve_guided", "hrt_accum_resolve_guided_host", "hrt_debug_guided", "hrt_debug_accum_features",
+    "hrt_accum_snapshot", "hrt_accum_restore", "hrt_accum_snapshot_info", "hrt_accum_merge_tiles",
 ]
 
 ABI_VERSION = 6  # include/hrt/hrt.h HRT_ABI_VERSION: the struct layouts below
@@ -308,6 +316,10 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "hrt_accum_resolve_guided_host": (S, [vp, ctypes.POINTER(GuidedParams), i32, vp]),
         "hrt_debug_guided": (S, [i32, vp, vp, vp, u32, u32, u32, f, f, f, f, vp]),
         "hrt_debug_accum_features": (S, [vp, vp, vp]),
+        "hrt_accum_snapshot": (S, [vp, vp, u64, ctypes.POINTER(u64)]),
+        "hrt_accum_restore": (S, [vp, vp, u64]),
+        "hrt_accum_snapshot_info": (S, [vp, u64, ctypes.POINTER(SnapshotInfo), vp, u32]),
+        "hrt_accum_merge_tiles": (S, [vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         if name in OPTIONAL and HRT_LIB_OVERRIDE and not hasattr(L, name):
@@ -706,14 +718,35 @@ class Accumulator:
         return out
 
     def refine(self, cam: Camera, p: RenderParams, target: float, pass_spp: int, max_spp: int, floor: float = 0.05,
-               min_spp: int = 0, on_pass=None):
+               min_spp: int = 0, on_pass=None, resume: bool = False):
         """Noise-driven passes of pass_spp samples (p's samples and sample_offset are ignored): one pass over every
         tile, then passes over the tiles whose mean error exceeds `target` (or that hold fewer than min_spp samples)
         and whose samples have not reached max_spp, until no such tile is left.  A tile's k-th pass is always samples
         [k * pass_spp, (k + 1) * pass_spp), so its pixels depend on its pass count alone.  on_pass(tile indices,
-        records) is called after every pass.  Returns the per-tile records (noise(floor))."""
+        records) is called after every pass.  Returns the per-tile records (noise(floor)).
+        resume=True goes on from whatever the tiles hold (an interrupted refine, restored from a snapshot) instead of
+        raising: the selection rule is applied to noise(floor) first, and every round sends one pass per distinct
+        sample count held among the selected tiles, in ascending order, at sample_offset = that count; so a tile's
+        k-th pass is the same samples and the resumed frame equals the uninterrupted one."""
         q = RenderParams.from_buffer_copy(p)
         q.samples = int(pass_spp)
+        if resume and any(self.tile_samples):
+            def keep(rec, among):
+                return [t for t in among if (rec[t].mean > target or rec[t].samples < min_spp) and rec[t].samples < max_spp]
+
+            rec = self.noise(floor)
+            todo = keep(rec, range(len(self.tiles)))
+            while todo:
+                held = self.tile_samples
+                for count in sorted({held[t] for t in todo}):
+                    group = [t for t in todo if held[t] == count]
+                    q.sample_offset = count
+                    self.add(cam, q, tiles=group)
+                    rec = self.noise(floor)
+                    if on_pass is not None:
+                        on_pass(group, rec)
+                todo = keep(rec, todo)
+            return rec
         todo = list(range(len(self.tiles)))
         first = True
         while True:
@@ -787,6 +820,60 @@ class Accumulator:
         """self += other (same scene device, tiles and frame identity; disjoint sample ranges)."""
         _check(load().hrt_accum_merge(self.h, other.h, None))
 
+    def merge_tiles(self, other: "Accumulator"):
+        """merge for accumulators whose tiles may hold different passes (hrt_accum_merge_tiles): every tile for which
+        `other` holds samples takes them (its ranges must be disjoint from this one's for that tile); the others are not
+        touched."""
+        _check(load().hrt_accum_merge_tiles(self.h, other.h, None))
+
+    def snapshot_size(self) -> int:
+        n = ctypes.c_uint64()
+        _check(load().hrt_accum_snapshot(self.h, None, 0, ctypes.byref(n)))
+        return n.value
+
+    def snapshot_into(self, buf: np.ndarray) -> int:
+        """hrt_accum_snapshot into a caller-owned contiguous uint8 array; returns the snapshot's bytes."""
+        if buf.dtype != np.uint8 or not buf.flags.c_contiguous or not buf.flags.writeable:
+            raise ValueError("a writable contiguous uint8 array")
+        n = ctypes.c_uint64()
+        _check(load().hrt_accum_snapshot(self.h, buf.ctypes.data, buf.size, ctypes.byref(n)))
+        return n.value
+
+    def snapshot(self) -> bytes:
+        """The whole state (sums, noise plane, feature planes, per-tile ranges and chunk counts, frame identity) as one
+        self-describing blob (hrt_accum_snapshot; include/hrt/hrt.h states the layout).  Waits for the device."""
+        buf = np.empty(self.snapshot_size(), np.uint8)
+        n = self.snapshot_into(buf)
+        return buf[:n].tobytes()
+
+    def restore(self, blob):
+        """Put a snapshot into this accumulator, which must hold no samples and have the snapshot's width, height, tiles
+        and flags (hrt_accum_restore); every later call then answers as on the snapshotted accumulator, bit for bit."""
+        b = np.frombuffer(blob, np.uint8)
+        _check(load().hrt_accum_restore(self.h, b.ctypes.data if b.size else None, b.size))
+
+    def save(self, path):
+        """The snapshot to a file (straight from the buffer the library filled, without snapshot()'s bytes object)."""
+        buf = np.empty(self.snapshot_size(), np.uint8)
+        n = self.snapshot_into(buf)
+        with open(path, "wb") as f:
+            f.write(memoryview(buf[:n]))
+
+    @classmethod
+    def load(cls, scene: Scene, path) -> "Accumulator":
+        """An accumulator on `scene` (the committed scene the snapshot was rendered on) from a file written by save:
+        created with the blob's size, tiles and flags (hrt_accum_snapshot_info), then restored."""
+        with open(path, "rb") as f:
+            blob = f.read()
+        info, tiles = snapshot_info(blob)
+        acc = cls(scene, info.width, info.height, tiles, noise=bool(info.flags & ACCUM_NOISE), features=bool(info.flags & ACCUM_FEATURES))
+        try:
+            acc.restore(blob)
+        except Exception:
+            acc.close()
+            raise
+        return acc
+
     def download(self):
         """(sums, ranges): the raw sums as (n_pixels, 4) float32 (w = 0) and the [(begin, end), ...] held."""
         n = ctypes.c_uint32()
@@ -807,6 +894,21 @@ class Accumulator:
 
     def reset(self):
         _check(load().hrt_accum_reset(self.h, None))
+
+
+def snapshot_info(blob):
+    """hrt_accum_snapshot_info: (SnapshotInfo, [(x, y, w, h), ...]) of a snapshot blob, validated as a restore
+    validates it; no device involved."""
+    b = np.frombuffer(blob, np.uint8)
+    ptr = b.ctypes.data if b.size else None
+    info = SnapshotInfo()
+    cap = 4096  # most tile lists fit: one validation (and one checksum pass over the blob), not two
+    arr = (Tile * cap)()
+    _check(load().hrt_accum_snapshot_info(ptr, b.size, ctypes.byref(info), ctypes.cast(arr, ctypes.c_void_p), cap))
+    if info.n_tiles > cap:
+        arr = (Tile * info.n_tiles)()
+        _check(load().hrt_accum_snapshot_info(ptr, b.size, ctypes.byref(info), ctypes.cast(arr, ctypes.c_void_p), info.n_tiles))
+    return info, [(t.x, t.y, t.w, t.h) for t in arr[: info.n_tiles]]
 
 
 def debug_accumulate(partial: np.ndarray, acc: np.ndarray, samples: int = 0, fmt: Optional[str] = None, on_device: bool = False):

@@ -403,8 +403,9 @@ hrt_status hrt_accum_upload(hrt_accum* a, const hrt_camera* cam, const hrt_rende
  * same ranges and chunk count again, the accumulator is an ordinary one again.
  * HRT_ACCUM_NOISE accumulators otherwise behave as plain ones (same sums, same frames, bit for bit) except: merge
  * needs both sides to have the flag (HRT_ERR_INVALID_ARG otherwise) and also adds m2 and K; hrt_accum_download works,
- * but the noise plane and K do not travel, so hrt_accum_upload into one is HRT_ERR_UNSUPPORTED.  Checkpointing the
- * noise plane, and accumulators whose tiles hold different passes, is out of scope.  hrt_accum_reset also clears
+ * but the noise plane and K do not travel, so hrt_accum_upload into one is HRT_ERR_UNSUPPORTED.  These calls keep
+ * their refusals: the whole state (noise plane, K, per-tile ranges, feature planes) travels through hrt_accum_snapshot /
+ * hrt_accum_restore, and tiles that hold different passes merge through hrt_accum_merge_tiles.  hrt_accum_reset also clears
  * m2, K and the per-tile ranges.  Frame identity, streams and the watchdog's invalid state apply unchanged. */
 /* Render samples [p->sample_offset, + p->samples) of tiles[idx[0..n)] of the accumulator only (indices into the
  * tile list it was created with) and add them: one megakernel launch and one accumulate kernel, whatever n.
@@ -531,6 +532,80 @@ struct hrt_guided_params { /* 20 bytes */
 hrt_status hrt_accum_resolve_guided(hrt_accum* a, const hrt_guided_params* g, int32_t format, void* d_out, void* stream);
 /* ... into HOST memory; waits for the device as hrt_accum_resolve_host does */
 hrt_status hrt_accum_resolve_guided_host(hrt_accum* a, const hrt_guided_params* g, int32_t format, void* out);
+
+/* ---- snapshots: checkpoint, restore and transport of the WHOLE accumulator state ----
+ * hrt_accum_snapshot writes everything the accumulator's later answers depend on into one self-describing blob in host
+ * memory; hrt_accum_restore puts it into an empty accumulator created with the same width, height, tile list and flags
+ * (on the same committed scene, as hrt_accum_upload requires; the blob carries no scene fingerprint).
+ * THE RESTORE CONTRACT: after a restore every later call returns the bits, and the status, it would have returned on the
+ * snapshotted accumulator: resolve, resolve_filtered, resolve_guided, noise, tile_samples, samples, feature_samples,
+ * features, and every later add, add_tiles, add_features and merge* with its acceptance or refusal.  So "render S1,
+ * snapshot, destroy, create, restore, render S2" equals "render S1, render S2" bit for bit in every plane.  The filters'
+ * raster buffers are scratch and are not part of a snapshot.
+ *
+ * THE LAYOUT (format version 1; every integer little-endian, u32 unless said; csrc/accum_snapshot.h is the codec):
+ *     0  magic 0x53545248 ("HRTS"), version 1
+ *     8  u64 bytes: the size of the whole blob, checksum included
+ *    16  flags (HRT_ACCUM_NOISE | HRT_ACCUM_FEATURES), width, height, n_tiles
+ *    32  u64 n_pixels: the sum of w * h over the tiles
+ *    40  has_identity (0 / 1), n_records (1, or n_tiles while the tiles hold different passes), n_feature_ranges, 0
+ *    56  the frame identity, 128 bytes (all 0 when has_identity is 0): hrt_camera's 96 bytes, max_depth, flags,
+ *        f32 t_min, f32 background[3], u64 seed
+ *   184  the tile list: n_tiles x (x, y, w, h)
+ *        the radiance ledger: n_records x { u64 K (chunks), u64 n_ranges, n_ranges x (u64 begin, u64 end) }, each list
+ *        sorted, disjoint, coalesced, non-empty ranges with end <= 2^32 (u64: 2^32 needs no wrap rule); a record without
+ *        ranges has K = 0
+ *        the feature ledger: n_feature_ranges x (u64 begin, u64 end), the same rules (0 without HRT_ACCUM_FEATURES)
+ *        zeros up to the next multiple of 16
+ *        the sums, n_pixels x 16 B, packed as the tiles are
+ *        with HRT_ACCUM_NOISE: m2, n_pixels x 4 B, then zeros up to the next multiple of 16
+ *        with HRT_ACCUM_FEATURES: fa, then fn, n_pixels x 16 B each
+ *        u64 checksum of the W = (bytes - 8) / 8 little-endian u64 words w_0 .. w_{W-1} before it: with
+ *        P = 0x100000001B3, four lanes h_i = 0xCBF29CE484222325 + i; word j does h_{j mod 4} = (h_{j mod 4} ^ w_j) * P;
+ *        then r = h_0, r = (r * P) ^ h_i for i = 1, 2, 3, r = (r ^ W) * P, checksum = r ^ (r >> 32), all mod 2^64.
+ * A blob is untrusted input: the decoder checks every length against `size` before it reads.  MALFORMED, each
+ * HRT_ERR_INVALID_ARG: shorter than its header, tile list or ledgers say; wrong magic or version; `size` not the bytes
+ * field, or not what the layout adds up to; unknown flags, a width or height outside [2, 65535], no tiles, a tile outside
+ * the image, n_pixels not the tiles' sum; ranges unsorted, overlapping, adjacent, empty or past 2^32; n_records neither 1
+ * nor n_tiles; K without ranges; feature ranges without the flag; has_identity == 0 together with samples or identity
+ * bytes; a bad checksum.
+ * Errors, each changing nothing: a snapshot of an accumulator in the watchdog's invalid state is HRT_ERR_STATE; a restore
+ * into an accumulator that holds radiance or feature samples (reset it first), or that is invalid, is HRT_ERR_STATE; a
+ * malformed blob, or one whose flags, width, height or tile list are not the accumulator's, is HRT_ERR_INVALID_ARG.
+ * hrt_accum_snapshot waits for the device, as hrt_accum_download does; hrt_accum_restore is synchronous. */
+/* *size = the snapshot's bytes.  out == NULL: only that.  Otherwise cap >= *size, else HRT_ERR_INVALID_ARG with nothing
+ * written to out. */
+hrt_status hrt_accum_snapshot(hrt_accum* a, void* out, uint64_t cap, uint64_t* size);
+hrt_status hrt_accum_restore(hrt_accum* a, const void* blob, uint64_t size);
+/* What an accumulator must be created with to take this blob (a struct the CALLER allocates; 40 bytes). */
+typedef struct hrt_snapshot_info hrt_snapshot_info;
+struct hrt_snapshot_info {
+  uint32_t version, flags, width, height, n_tiles;
+  uint32_t uniform; /* 1: every tile holds the same passes (n_records == 1) */
+  uint64_t n_pixels, bytes;
+};
+/* Validates the blob as a restore does (no device involved) and describes it; the tile list goes to `tiles` when
+ * cap >= n_tiles (tiles may be NULL with cap 0 to ask for n_tiles first). */
+hrt_status hrt_accum_snapshot_info(const void* blob, uint64_t size, hrt_snapshot_info* info, hrt_tile* tiles, uint32_t cap);
+
+/* ---- merging accumulators whose tiles hold different passes ----
+ * hrt_accum_merge for accumulators whose tiles may hold different passes, on either side, with or without the noise and
+ * feature planes.  Preconditions as hrt_accum_merge's: the same device, image size and tile list, HRT_ACCUM_NOISE and
+ * HRT_ACCUM_FEATURES equal on both sides, the same frame identity, both usable.
+ * THE CONTRACT:
+ *   - for every tile t, src's ranges of t must be disjoint from dst's ranges of t: otherwise HRT_ERR_INVALID_ARG and
+ *     nothing changes;
+ *   - a tile for which src holds no samples is NOT TOUCHED: its sums, its m2, its ranges and its K are never written (a
+ *     -0.0f or NaN bit pattern survives);
+ *   - every other tile takes acc = acc + src.acc per channel (dst's operand first) and m2 = m2 + src.m2, its ranges
+ *     become the union and K = K + K_src;
+ *   - the feature planes and the feature ranges merge exactly as in hrt_accum_merge (every tile, dst + src);
+ *   - if every tile then holds the same ranges and K, the accumulator is an ordinary one again (hrt_accum_samples,
+ *     download, merge work);
+ *   - two accumulators whose tiles each hold the same passes give hrt_accum_merge's bits.
+ * One kernel launch for sums and m2 whatever the subset, stream-ordered on `stream`; the host bookkeeping is updated at
+ * call time. */
+hrt_status hrt_accum_merge_tiles(hrt_accum* dst, const hrt_accum* src, void* stream);
 
 /* ---- diagnostics ---- */
 /* Device occupancy / layout facts of the committed scene (for DESIGN/bench). */
