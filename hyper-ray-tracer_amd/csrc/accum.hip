@@ -378,6 +378,8 @@ void launch_resolve(hrt_accum* a, int32_t format, void* d_out, hipStream_t strea
   resolve_pixels(format, a->d_acc, a->n_px, accum::resolve_scale(a->ledger.samples(0)), d_out, stream);
 }
 
+constexpr filter::Demod NO_DEMOD{false, 0.0f};
+
 /* hrt_accum_resolve_filtered's checks: nothing changes on an error */
 void filter_args(const hrt_filter_params* f) {
   if (f->iterations < 1 || f->iterations > filter::MAX_ITERATIONS)
@@ -446,8 +448,9 @@ void filter_prepare(hrt_accum* a, hipStream_t stream) {
   a->f_w = w, a->f_h = h, a->f_blocks = (uint32_t)blocks;
   a->f_state = 1;
 }
-/* the sums and m2 gathered onto plane 0 */
-void filter_gather_plane(hrt_accum* a, hipStream_t stream) {
+uint64_t feature_samples(const hrt_accum* a) { return a->f_ledger.samples(0); }
+/* the sums and m2 gathered onto plane 0; demod.on: demodulated by the mean albedo in the same pass */
+void filter_gather_plane(hrt_accum* a, const filter::Demod& demod, hipStream_t stream) {
   filter_prepare(a, stream);
   upload_noise_tiles(a, stream); /* each tile's own 1 / N and 1 / (K - 1) */
   const uint32_t nt = (uint32_t)a->tiles.size();
@@ -457,14 +460,18 @@ void filter_gather_plane(hrt_accum* a, hipStream_t stream) {
   }
   hip_check(hipMemcpyAsync(a->d_ftiles, a->h_ftiles.data(), nt * sizeof(filter::FilterTile), hipMemcpyHostToDevice, stream),
             "hipMemcpyAsync(filter tiles)");
-  filter::launch_gather(a->d_acc, a->d_m2, a->d_ftiles, nt, a->f_blocks, a->d_fplane[0], a->f_w, stream);
+  if (demod.on)
+    filter::launch_gather_demod(a->d_acc, a->d_m2, a->d_fa, 1.0f / (float)feature_samples(a), demod.floor, a->d_ftiles, nt, a->f_blocks,
+                                a->d_fplane[0], a->f_w, stream);
+  else
+    filter::launch_gather(a->d_acc, a->d_m2, a->d_ftiles, nt, a->f_blocks, a->d_fplane[0], a->f_w, stream);
 }
-uint64_t feature_samples(const hrt_accum* a) { return a->f_ledger.samples(0); }
 /* the filtered resolve, or with the terms K the guided one: the colour plane gathered, the feature rasters if guided,
- * then the iterations */
-void launch_filtered(hrt_accum* a, uint32_t iterations, float sigma, const filter::Terms* K, int32_t format, void* d_out,
-                     hipStream_t stream) {
-  filter_gather_plane(a, stream);
+ * then the iterations.  demod (a guided resolve's option, filter.h): the plane is gathered demodulated and the last
+ * iteration remodulates */
+void launch_filtered(hrt_accum* a, uint32_t iterations, float sigma, const filter::Terms* K, const filter::Demod& demod, int32_t format,
+                     void* d_out, hipStream_t stream) {
+  filter_gather_plane(a, K ? demod : NO_DEMOD, stream);
   const uint32_t nt = (uint32_t)a->tiles.size();
   if (K && !a->d_gplane[0]) { /* the two feature rasters, once: a present pixel's features are written by every resolve */
     float4* plane[2] = {nullptr, nullptr};
@@ -481,7 +488,7 @@ void launch_filtered(hrt_accum* a, uint32_t iterations, float sigma, const filte
     filter::launch_gather_features(a->d_fa, a->d_fn, a->d_ftiles, nt, a->f_blocks, 1.0f / (float)feature_samples(a), albedo, normal,
                                    a->f_w, stream);
   filter::launch_atrous(a->d_fplane[0], a->d_fplane[1], albedo, normal, a->f_w, a->f_h, a->d_ftiles, nt, a->f_blocks, iterations, sigma,
-                        K ? *K : filter::Terms{}, format, d_out, stream);
+                        K ? *K : filter::Terms{}, K ? demod : NO_DEMOD, format, d_out, stream);
 }
 
 /* hrt_accum_resolve_guided's checks beyond the filtered resolve's, and its tolerances as filter.h takes them */
@@ -493,6 +500,21 @@ filter::Terms guided_args(const hrt_guided_params* g) {
   const hrt_filter_params f{g->iterations, g->sigma};
   filter_args(&f);
   return filter::Terms{guided_term(g->normal), guided_term(g->albedo), guided_term(g->depth)};
+}
+/* hrt_guided_ex_params' checks beyond guided_args': its flags, reserved and, with HRT_GUIDED_DEMODULATE, the floor (not
+ * read otherwise) */
+filter::Demod guided_ex_option(uint32_t flags, float albedo_floor) {
+  if (flags & ~(uint32_t)HRT_GUIDED_DEMODULATE) throw HipError{HRT_ERR_INVALID_ARG, "hrt_guided_ex_params: unknown HRT_GUIDED_* flag bits"};
+  if (!(flags & HRT_GUIDED_DEMODULATE)) return NO_DEMOD;
+  if (!(albedo_floor > 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_guided_ex_params: albedo_floor must be > 0 with HRT_GUIDED_DEMODULATE"};
+  return filter::Demod{true, albedo_floor};
+}
+filter::Terms guided_ex_args(const hrt_guided_ex_params* g, filter::Demod& demod) {
+  const hrt_guided_params base{g->iterations, g->sigma, g->normal, g->albedo, g->depth};
+  const filter::Terms K = guided_args(&base);
+  if (g->reserved != 0) throw HipError{HRT_ERR_INVALID_ARG, "hrt_guided_ex_params: reserved must be 0"};
+  demod = guided_ex_option(g->flags, g->albedo_floor);
+  return K;
 }
 void features_flag(const hrt_accum* a, const char* who) {
   if (!a->d_fa) throw HipError{HRT_ERR_STATE, std::string(who) + ": the accumulator was created without HRT_ACCUM_FEATURES"};
@@ -838,7 +860,7 @@ hrt_status hrt_accum_resolve_filtered(hrt_accum* a, const hrt_filter_params* f, 
     filter_args(f);
     filter_state(a);
     DeviceGuard dg(a->device);
-    launch_filtered(a, f->iterations, f->sigma, nullptr, format, d_out, (hipStream_t)stream);
+    launch_filtered(a, f->iterations, f->sigma, nullptr, NO_DEMOD, format, d_out, (hipStream_t)stream);
   });
 }
 
@@ -849,7 +871,7 @@ hrt_status hrt_accum_resolve_filtered_host(hrt_accum* a, const hrt_filter_params
     filter_args(f);
     filter_state(a);
     resolve_to_host(a, format, out, "hipMemcpy(filtered resolve)",
-                    [&](void* d_out) { launch_filtered(a, f->iterations, f->sigma, nullptr, format, d_out, nullptr); });
+                    [&](void* d_out) { launch_filtered(a, f->iterations, f->sigma, nullptr, NO_DEMOD, format, d_out, nullptr); });
   });
 }
 
@@ -926,7 +948,7 @@ hrt_status hrt_accum_resolve_guided(hrt_accum* a, const hrt_guided_params* g, in
     const filter::Terms K = guided_args(g);
     guided_state(a);
     DeviceGuard dg(a->device);
-    launch_filtered(a, g->iterations, g->sigma, &K, format, d_out, (hipStream_t)stream);
+    launch_filtered(a, g->iterations, g->sigma, &K, NO_DEMOD, format, d_out, (hipStream_t)stream);
   });
 }
 
@@ -937,7 +959,31 @@ hrt_status hrt_accum_resolve_guided_host(hrt_accum* a, const hrt_guided_params* 
     const filter::Terms K = guided_args(g);
     guided_state(a);
     resolve_to_host(a, format, out, "hipMemcpy(guided resolve)",
-                    [&](void* d_out) { launch_filtered(a, g->iterations, g->sigma, &K, format, d_out, nullptr); });
+                    [&](void* d_out) { launch_filtered(a, g->iterations, g->sigma, &K, NO_DEMOD, format, d_out, nullptr); });
+  });
+}
+
+hrt_status hrt_accum_resolve_guided_ex(hrt_accum* a, const hrt_guided_ex_params* g, int32_t format, void* d_out, void* stream) {
+  return hguard([&] {
+    if (!a || !g || !d_out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_resolve_guided_ex: null argument"};
+    accum_format(format);
+    filter::Demod demod = NO_DEMOD;
+    const filter::Terms K = guided_ex_args(g, demod);
+    guided_state(a);
+    DeviceGuard dg(a->device);
+    launch_filtered(a, g->iterations, g->sigma, &K, demod, format, d_out, (hipStream_t)stream);
+  });
+}
+
+hrt_status hrt_accum_resolve_guided_ex_host(hrt_accum* a, const hrt_guided_ex_params* g, int32_t format, void* out) {
+  return hguard([&] {
+    if (!a || !g || !out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_resolve_guided_ex_host: null argument"};
+    accum_format(format);
+    filter::Demod demod = NO_DEMOD;
+    const filter::Terms K = guided_ex_args(g, demod);
+    guided_state(a);
+    resolve_to_host(a, format, out, "hipMemcpy(guided resolve)",
+                    [&](void* d_out) { launch_filtered(a, g->iterations, g->sigma, &K, demod, format, d_out, nullptr); });
   });
 }
 
@@ -1247,18 +1293,21 @@ hrt_status hrt_debug_noise(int32_t on_device, const float* partial, const uint32
   });
 }
 
-/* hrt_debug_filter and hrt_debug_guided after their checks; albedo and normal null: the plain filter */
+/* hrt_debug_filter, hrt_debug_guided and hrt_debug_guided_ex after their checks; albedo and normal null: the plain
+ * filter */
 static void debug_atrous(int32_t on_device, const float* raster, const float* albedo, const float* normal, uint32_t width,
-                         uint32_t height, uint32_t iterations, float sigma, const filter::Terms& K, float* out) {
-  if (!on_device) return filter::filter_raster(raster, albedo, normal, width, height, iterations, sigma, K, out);
+                         uint32_t height, uint32_t iterations, float sigma, const filter::Terms& K, const filter::Demod& demod,
+                         float* out) {
+  if (!on_device) return filter::filter_raster(raster, albedo, normal, width, height, iterations, sigma, K, demod, out);
   /* the real kernels on the calling thread's current device: one tile that covers the raster, so the packed
    * order of the last iteration's output is the raster's */
   const size_t bytes = (size_t)width * height * sizeof(float4);
   const filter::FilterTile T{0, 0, width, height, 0, 0, 0.0f, 0.0f};
   DevBuf<float4> d_a(bytes, raster), d_b(bytes), d_al(albedo ? bytes : 0, albedo), d_no(normal ? bytes : 0, normal), d_out(bytes);
   DevBuf<filter::FilterTile> d_tile(sizeof(filter::FilterTile), &T);
+  if (demod.on) filter::launch_demodulate(d_a.p, d_al.p, (size_t)width * height, demod.floor, nullptr);
   filter::launch_atrous(d_a.p, d_b.p, albedo ? d_al.p : nullptr, normal ? d_no.p : nullptr, width, height, d_tile.p, 1,
-                        filter::tile_blocks(width, height), iterations, sigma, K, filter::FORMAT_RAW, d_out.p, nullptr);
+                        filter::tile_blocks(width, height), iterations, sigma, K, demod, filter::FORMAT_RAW, d_out.p, nullptr);
   hip_check(hipMemcpy(out, d_out.p, bytes, hipMemcpyDeviceToHost), "hipMemcpy");
 }
 
@@ -1269,7 +1318,7 @@ hrt_status hrt_debug_filter(int32_t on_device, const float* raster, uint32_t wid
       throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_filter: null argument, or a width or height outside [1, 65535]"};
     const hrt_filter_params f{iterations, sigma};
     filter_args(&f);
-    debug_atrous(on_device, raster, nullptr, nullptr, width, height, iterations, sigma, filter::Terms{}, out);
+    debug_atrous(on_device, raster, nullptr, nullptr, width, height, iterations, sigma, filter::Terms{}, NO_DEMOD, out);
   });
 }
 
@@ -1281,7 +1330,21 @@ hrt_status hrt_debug_guided(int32_t on_device, const float* raster, const float*
     const hrt_filter_params f{iterations, sigma};
     filter_args(&f);
     if (!(kn >= 0.0f) || !(ka >= 0.0f) || !(kz >= 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_guided: a negative or NaN term"};
-    debug_atrous(on_device, raster, albedo, normal, width, height, iterations, sigma, filter::Terms{kn, ka, kz}, out);
+    debug_atrous(on_device, raster, albedo, normal, width, height, iterations, sigma, filter::Terms{kn, ka, kz}, NO_DEMOD, out);
+  });
+}
+
+hrt_status hrt_debug_guided_ex(int32_t on_device, const float* raster, const float* albedo, const float* normal, uint32_t width,
+                               uint32_t height, uint32_t iterations, float sigma, float kn, float ka, float kz, uint32_t flags,
+                               float albedo_floor, float* out) {
+  return hguard([&] {
+    if (!raster || !albedo || !normal || !out || width == 0 || height == 0 || width > 65535 || height > 65535)
+      throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_guided_ex: null argument, or a width or height outside [1, 65535]"};
+    const hrt_filter_params f{iterations, sigma};
+    filter_args(&f);
+    if (!(kn >= 0.0f) || !(ka >= 0.0f) || !(kz >= 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_guided_ex: a negative or NaN term"};
+    const filter::Demod demod = guided_ex_option(flags, albedo_floor);
+    debug_atrous(on_device, raster, albedo, normal, width, height, iterations, sigma, filter::Terms{kn, ka, kz}, demod, out);
   });
 }
 

@@ -35,6 +35,21 @@
  * These weights are polynomials for the same reason.  The feature planes are constant across iterations; only (c, v)
  * ping-pongs.  Both filters are ONE function, atrous_pixel: the plain one is the guided one whose per-tap hook adds no
  * term.
+ *
+ * The bits of a DEMODULATED guided frame (hrt_accum_resolve_guided_ex with HRT_GUIDED_DEMODULATE; hrt_debug_guided_ex):
+ * the filter runs on the radiance divided by the first-hit albedo, so that it averages irradiance across texture edges,
+ * and the texture is multiplied back at full sharpness.  With a_p the xyz of pixel p's mean albedo (the bits
+ * hrt_accum_features returns) and `floor` the caller's albedo floor (> 0):
+ *   1. m_p = (at_least(a_p.x, floor), at_least(a_p.y, floor), at_least(a_p.z, floor)) (demod_divisor); a NaN albedo
+ *      gives floor.
+ *   2. The input of a present pixel replaces gather's (demodulate): d_p = (c_p.x / m_p.x, c_p.y / m_p.y, c_p.z / m_p.z);
+ *      l = luma(c_p), l' = luma(d_p), g = l > 0 ? l' / l : 0.0f; v'_p = v_p * (g * g), which keeps the relative standard
+ *      error of the luminance and is exact for a grey albedo.  Absent pixels stay absent, as they are.
+ *   3. The iterations are exactly the ones above on the planes (d, v'), the feature terms reading the same mean planes.
+ *   4. The last iteration's d' is remodulated (remodulate): c'' = (d'.x * m_p.x, d'.y * m_p.y, d'.z * m_p.z), then the
+ *      output rule above on c''; the sw == 0 escape's pixel is remodulated like any other.  v' stays in demodulated
+ *      units.
+ * Without the flag none of this runs and floor is not read: the frame is the guided one bit for bit.
  */
 #pragma once
 #include <stddef.h>
@@ -70,6 +85,26 @@ HRT_HD Px gather(Vec3 acc, float m2, float inv_n, float inv_k1) {
   p.v = accum::variance(m2, accum::luma(acc), inv_n, inv_k1) * inv_n;
   return p;
 }
+
+/* demodulation by the first-hit albedo a (the mean albedo plane's xyz): the divisor, the filter's input pixel in place
+ * of gather's, and the last iteration's colour back in radiance */
+HRT_HD Vec3 demod_divisor(Vec3 a, float floor) {
+  return v3(accum::at_least(a.x, floor), accum::at_least(a.y, floor), accum::at_least(a.z, floor));
+}
+HRT_HD Px demodulate(const Px& p, Vec3 m) {
+  Px d;
+  d.c = v3(p.c.x / m.x, p.c.y / m.y, p.c.z / m.z);
+  const float l = accum::luma(p.c), ld = accum::luma(d.c);
+  const float g = l > 0.0f ? ld / l : 0.0f;
+  d.v = p.v * (g * g);
+  return d;
+}
+HRT_HD Vec3 remodulate(Vec3 d, Vec3 m) { return v3(d.x * m.x, d.y * m.y, d.z * m.z); }
+/* the option of a guided resolve: off, or on with the caller's albedo floor (> 0; not read when off) */
+struct Demod {
+  bool on;
+  float floor;
+};
 
 HRT_HD float g_tap(int k) { return k == 1 ? 2.0f : 1.0f; }
 HRT_HD float h_tap(int k) { return k == 2 ? 0.375f : ((k == 1 || k == 3) ? 0.25f : 0.0625f); }
@@ -168,11 +203,21 @@ HRT_HD Vec3 resolve(const Px& p) { return v3(sqrtf(p.c.x), sqrtf(p.c.y), sqrtf(p
 
 /* The host's restatement of a whole raster: in and out are width x height x 4 f32 (c.xyz, v); absent pixels pass
  * through as they are.  albedo and normal: the two feature rasters (a.xyz, -) and (n.xyz, z) of the guided filter, read
- * at present pixels only, or both null: the plain filter (K is not read). */
+ * at present pixels only, or both null: the plain filter (K is not read).  demod.on (the guided filter only): `in` is
+ * gather's (c, v); its present pixels are demodulated before the first iteration and the last one's colour is
+ * remodulated, so out is (c''.xyz, v' in demodulated units). */
 inline void filter_raster(const float* in, const float* albedo, const float* normal, uint32_t width, uint32_t height,
-                          uint32_t iterations, float sigma, const Terms& K, float* out) {
+                          uint32_t iterations, float sigma, const Terms& K, const Demod& demod, float* out) {
   const size_t n = (size_t)width * height;
   std::vector<float> a(in, in + 4 * n), b(4 * n);
+  auto divisor = [=](size_t k) { return demod_divisor(v3(albedo[k], albedo[k + 1], albedo[k + 2]), demod.floor); };
+  if (demod.on)
+    for (size_t k = 0; k < 4 * n; k += 4) {
+      const Px p = px(a[k], a[k + 1], a[k + 2], a[k + 3]);
+      if (!present(p)) continue;
+      const Px d = demodulate(p, divisor(k));
+      a[k] = d.c.x, a[k + 1] = d.c.y, a[k + 2] = d.c.z, a[k + 3] = d.v;
+    }
   auto feat = [=](int x, int y) {
     const size_t k = 4 * ((size_t)y * width + (size_t)x);
     Feat f;
@@ -199,6 +244,12 @@ inline void filter_raster(const float* in, const float* albedo, const float* nor
       }
     a.swap(b);
   }
+  if (demod.on)
+    for (size_t k = 0; k < 4 * n; k += 4) {
+      if (!present(px(a[k], a[k + 1], a[k + 2], a[k + 3]))) continue;
+      const Vec3 c = remodulate(v3(a[k], a[k + 1], a[k + 2]), divisor(k));
+      a[k] = c.x, a[k + 1] = c.y, a[k + 2] = c.z;
+    }
   for (size_t k = 0; k < 4 * n; k++) out[k] = a[k];
 }
 
@@ -222,14 +273,22 @@ constexpr int32_t FORMAT_RAW = -1;
 /* acc, m2 (packed) -> plane (plane_w x plane_h float4) at the tiles' pixels */
 void launch_gather(const void* d_acc, const float* d_m2, const FilterTile* d_tiles, uint32_t n_tiles, uint32_t n_blocks,
                    void* d_plane, uint32_t plane_w, void* stream);
+/* launch_gather with the pixel demodulated by the mean albedo of the packed feature sums d_fa (inv = 1 / feature
+ * samples): the same pass over the packed sums */
+void launch_gather_demod(const void* d_acc, const float* d_m2, const void* d_fa, float inv, float floor, const FilterTile* d_tiles,
+                         uint32_t n_tiles, uint32_t n_blocks, void* d_plane, uint32_t plane_w, void* stream);
+/* the present pixels of a raster plane of n pixels that holds gather's (c, v), demodulated in place by the albedo raster
+ * (hrt_debug_guided_ex; an accumulator's plane is demodulated where it is gathered) */
+void launch_demodulate(void* d_plane, const void* d_albedo, size_t n, float floor, void* stream);
 /* the packed feature sums (fa, fn) -> the two mean rasters (plane_w wide) at the tiles' pixels; inv = 1 / feature samples */
 void launch_gather_features(const void* d_fa, const void* d_fn, const FilterTile* d_tiles, uint32_t n_tiles, uint32_t n_blocks,
                             float inv, void* d_albedo, void* d_normal, uint32_t plane_w, void* stream);
 /* `iterations` of the filter from plane a (b is the other plane; both are written), the last one to d_out packed.
- * d_albedo and d_normal: the guided filter's feature rasters, or both null: the plain filter (K is not read). */
+ * d_albedo and d_normal: the guided filter's feature rasters, or both null: the plain filter (K is not read).
+ * demod.on (the guided filter only): plane a is demodulated, and the last iteration remodulates what it writes. */
 void launch_atrous(void* d_a, void* d_b, const void* d_albedo, const void* d_normal, uint32_t plane_w, uint32_t plane_h,
                    const FilterTile* d_tiles, uint32_t n_tiles, uint32_t n_blocks, uint32_t iterations, float sigma, const Terms& K,
-                   int32_t format, void* d_out, void* stream);
+                   const Demod& demod, int32_t format, void* d_out, void* stream);
 
 }  // namespace filter
 }  // namespace hrt

@@ -13,6 +13,11 @@
  *   guided_atrous   the same body (atrous_iteration) with the feature terms.  A staged step may stage the two feature
  *                   planes behind the colour plane (dynamic LDS: 1 or 3 planes); otherwise a tap's features come from
  *                   global memory.
+ *   demod_gather, guided_atrous_demod   a DEMODULATED guided resolve (filter.h) adds no pass and no raster: its gather
+ *                   divides the pixel by its mean albedo where the colour plane is written, from the packed feature sums,
+ *                   and its LAST iteration multiplies the albedo of the centre pixel (at hand for the feature terms, in
+ *                   LDS when the features are staged) back where the packed output is written.  The inner iterations are
+ *                   guided_atrous itself.  demod_raster does the gather's part for a raster of hrt_debug_guided_ex.
  *
  * LDS layout: rows of (32 + 4 * step) float4, linear.  A wave is two block rows of 32 lanes; a tap is the same offset
  * for every lane, so each 16-lane group of a 16-byte LDS read (lanes {0-3, 12-15, 20-27} etc.) reads 16 distinct
@@ -86,6 +91,33 @@ __global__ __launch_bounds__(BLOCK) void filter_gather(const float4* __restrict_
   plane[(size_t)(T.y + ly) * plane_w + (T.x + lx)] = as_f4(gather(v3(a.x, a.y, a.z), m2[i], T.inv_n, T.inv_k1));
 }
 
+/* filter_gather for a demodulated resolve: the same pass, the pixel divided by its mean albedo (the bits guided_gather
+ * writes to the albedo raster, from the same packed sums) */
+__global__ __launch_bounds__(BLOCK) void demod_gather(const float4* __restrict__ acc, const float* __restrict__ m2,
+                                                      const float4* __restrict__ fa, float inv, float floor,
+                                                      const FilterTile* __restrict__ tiles, uint32_t n_tiles,
+                                                      float4* __restrict__ plane, uint32_t plane_w) {
+  uint32_t bx, by;
+  const FilterTile T = tile_and_corner(tiles, n_tiles, blockIdx.x, bx, by);
+  const uint32_t lx = bx + threadIdx.x % BLOCK_W, ly = by + threadIdx.x / BLOCK_W;
+  if (lx >= T.w || ly >= T.h) return;
+  const size_t i = (size_t)T.off + (size_t)ly * T.w + lx;
+  const float4 a = acc[i], al = features::mean_albedo(fa[i], inv);
+  const Px p = gather(v3(a.x, a.y, a.z), m2[i], T.inv_n, T.inv_k1);
+  plane[(size_t)(T.y + ly) * plane_w + (T.x + lx)] = as_f4(demodulate(p, demod_divisor(v3(al.x, al.y, al.z), floor)));
+}
+
+/* a raster that holds gather's (c, v), demodulated in place by the albedo raster at its present pixels */
+__global__ __launch_bounds__(BLOCK) void demod_raster(float4* __restrict__ plane, const float4* __restrict__ albedo, size_t n,
+                                                      float floor) {
+  const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const Px p = load_px(plane, i);
+  if (!present(p)) return;
+  const float4 al = albedo[i];
+  plane[i] = as_f4(demodulate(p, demod_divisor(v3(al.x, al.y, al.z), floor)));
+}
+
 __global__ __launch_bounds__(BLOCK) void guided_gather(const float4* __restrict__ fa, const float4* __restrict__ fn,
                                                        const FilterTile* __restrict__ tiles, uint32_t n_tiles, float inv,
                                                        float4* __restrict__ albedo, float4* __restrict__ normal, uint32_t plane_w) {
@@ -105,10 +137,16 @@ struct NoPlanes {
   static constexpr bool guided = false;
 };
 struct FeaturePlanes {
-  static constexpr bool guided = true;
+  static constexpr bool guided = true, demod = false;
   const float4 *albedo, *normal;
   Terms K;
   uint32_t lds;
+};
+/* the feature planes of a demodulated resolve's LAST iteration, which remodulates the pixel it writes by the centre's
+ * albedo (filter.h): the flag is compile time, so the other instantiations are what they are without it */
+struct DemodPlanes : FeaturePlanes {
+  static constexpr bool demod = true;
+  float floor;
 };
 
 /* One iteration, the body of both kernels.  sh: the workgroup's LDS.
@@ -191,6 +229,10 @@ __device__ __forceinline__ void atrous_iteration(float4* sh, const Features F, c
       return as_feat(staged[RW * RH + k], staged[2 * RW * RH + k]);
     };
     o = present(p) ? atrous_pixel(at, feature_terms(feat, x, y, F.K), x, y, s, sigma) : p;
+    if constexpr (Features::demod) {
+      /* the centre's albedo is the one the feature terms hold already */
+      if (present(p)) o.c = remodulate(o.c, demod_divisor(feat(x, y).a, F.floor));
+    }
   } else {
     o = present(p) ? atrous_pixel(at, NoFeatures{}, x, y, s, sigma) : p;
   }
@@ -226,7 +268,20 @@ __global__ __launch_bounds__(BLOCK) void guided_atrous(const float4* __restrict_
                                  sigma, out);
 }
 
-/* one iteration's launch; albedo and normal null: the plain filter */
+/* guided_atrous as the last iteration of a demodulated resolve: the packed pixel is remodulated where it is written */
+template <int STEP, int32_t FORMAT>
+__global__ __launch_bounds__(BLOCK) void guided_atrous_demod(const float4* __restrict__ in, const float4* __restrict__ albedo,
+                                                             const float4* __restrict__ normal, uint32_t plane_w, uint32_t plane_h,
+                                                             const FilterTile* __restrict__ tiles, uint32_t n_tiles, int step,
+                                                             float sigma, Terms K, uint32_t feat_lds, float floor,
+                                                             void* __restrict__ out) {
+  static_assert(FORMAT != FORMAT_PLANE, "only the last iteration remodulates");
+  extern __shared__ float4 sh_planes[];
+  atrous_iteration<STEP, FORMAT>(sh_planes, DemodPlanes{{albedo, normal, K, feat_lds}, floor}, in, plane_w, plane_h, tiles, n_tiles,
+                                 step, sigma, out);
+}
+
+/* one iteration's launch; albedo and normal null: the plain filter; demod.on: the last iteration of a demodulated one */
 struct Iteration {
   const float4 *in, *albedo, *normal;
   uint32_t w, h;
@@ -237,6 +292,7 @@ struct Iteration {
   Terms K;
   void* out;
   hipStream_t stream;
+  Demod demod;
 };
 
 template <int STEP, int32_t FORMAT>
@@ -246,8 +302,17 @@ void launch_one(const Iteration& I, bool feat_lds) {
                        I.step, I.sigma, I.out);
     hip_check(hipGetLastError(), "filter_atrous launch");
   } else if constexpr (STEP <= GUIDED_STAGED_MAX) {
-    hipLaunchKernelGGL((guided_atrous<STEP, FORMAT>), dim3(I.blocks), dim3(BLOCK), lds_bytes(STEP, feat_lds ? 3 : 1), I.stream, I.in,
-                       I.albedo, I.normal, I.w, I.h, I.tiles, I.n_tiles, I.step, I.sigma, I.K, feat_lds ? 1u : 0u, I.out);
+    const size_t lds = lds_bytes(STEP, feat_lds ? 3 : 1);
+    if constexpr (FORMAT != FORMAT_PLANE) {
+      if (I.demod.on) {
+        hipLaunchKernelGGL((guided_atrous_demod<STEP, FORMAT>), dim3(I.blocks), dim3(BLOCK), lds, I.stream, I.in, I.albedo, I.normal, I.w,
+                           I.h, I.tiles, I.n_tiles, I.step, I.sigma, I.K, feat_lds ? 1u : 0u, I.demod.floor, I.out);
+        hip_check(hipGetLastError(), "guided_atrous_demod launch");
+        return;
+      }
+    }
+    hipLaunchKernelGGL((guided_atrous<STEP, FORMAT>), dim3(I.blocks), dim3(BLOCK), lds, I.stream, I.in, I.albedo, I.normal, I.w, I.h,
+                       I.tiles, I.n_tiles, I.step, I.sigma, I.K, feat_lds ? 1u : 0u, I.out);
     hip_check(hipGetLastError(), "guided_atrous launch");
   }
 }
@@ -278,6 +343,19 @@ void launch_gather(const void* d_acc, const float* d_m2, const FilterTile* d_til
   hip_check(hipGetLastError(), "filter_gather launch");
 }
 
+void launch_gather_demod(const void* d_acc, const float* d_m2, const void* d_fa, float inv, float floor, const FilterTile* d_tiles,
+                         uint32_t n_tiles, uint32_t n_blocks, void* d_plane, uint32_t plane_w, void* stream) {
+  hipLaunchKernelGGL(demod_gather, dim3(n_blocks), dim3(BLOCK), 0, (hipStream_t)stream, (const float4*)d_acc, d_m2, (const float4*)d_fa, inv,
+                     floor, d_tiles, n_tiles, (float4*)d_plane, plane_w);
+  hip_check(hipGetLastError(), "demod_gather launch");
+}
+
+void launch_demodulate(void* d_plane, const void* d_albedo, size_t n, float floor, void* stream) {
+  hipLaunchKernelGGL(demod_raster, dim3((uint32_t)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, (float4*)d_plane,
+                     (const float4*)d_albedo, n, floor);
+  hip_check(hipGetLastError(), "demod_raster launch");
+}
+
 void launch_gather_features(const void* d_fa, const void* d_fn, const FilterTile* d_tiles, uint32_t n_tiles, uint32_t n_blocks,
                             float inv, void* d_albedo, void* d_normal, uint32_t plane_w, void* stream) {
   hipLaunchKernelGGL(guided_gather, dim3(n_blocks), dim3(BLOCK), 0, (hipStream_t)stream, (const float4*)d_fa, (const float4*)d_fn, d_tiles,
@@ -287,17 +365,18 @@ void launch_gather_features(const void* d_fa, const void* d_fn, const FilterTile
 
 void launch_atrous(void* d_a, void* d_b, const void* d_albedo, const void* d_normal, uint32_t plane_w, uint32_t plane_h,
                    const FilterTile* d_tiles, uint32_t n_tiles, uint32_t n_blocks, uint32_t iterations, float sigma, const Terms& K,
-                   int32_t format, void* d_out, void* stream) {
+                   const Demod& demod, int32_t format, void* d_out, void* stream) {
   const uint32_t plane_blocks = ((plane_w + BLOCK_W - 1) / BLOCK_W) * ((plane_h + BLOCK_H - 1) / BLOCK_H);
   float4 *src = (float4*)d_a, *dst = (float4*)d_b;
   Iteration I{src, (const float4*)d_albedo, (const float4*)d_normal, plane_w, plane_h, d_tiles, n_tiles, plane_blocks, 1, sigma, K, dst,
-              (hipStream_t)stream};
+              (hipStream_t)stream, Demod{false, 0.0f}};
   for (uint32_t i = 0; i + 1 < iterations; i++) {
     I.in = src, I.out = dst, I.step = 1 << i;
     launch_step<FORMAT_PLANE>(I);
     std::swap(src, dst);
   }
   I.in = src, I.out = d_out, I.step = 1 << (iterations - 1), I.blocks = n_blocks;
+  if (d_albedo) I.demod = demod; /* the last iteration remodulates */
   if (format == FORMAT_RAW) launch_step<FORMAT_RAW>(I);
   else if (format == HRT_ACCUM_F32) launch_step<HRT_ACCUM_F32>(I);
   else launch_step<HRT_ACCUM_RGBA8>(I);

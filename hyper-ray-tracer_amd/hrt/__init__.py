@@ -160,6 +160,13 @@ class GuidedParams(ctypes.Structure):
                 ("albedo", ctypes.c_float), ("depth", ctypes.c_float)]
 
 
+class GuidedExParams(ctypes.Structure):
+    """hrt_guided_ex_params: hrt_guided_params, then the HRT_GUIDED_* flags, the albedo floor of GUIDED_DEMODULATE (> 0)
+    and a reserved word (0)."""
+    _fields_ = GuidedParams._fields_ + [("flags", ctypes.c_uint32), ("albedo_floor", ctypes.c_float),
+                                        ("reserved", ctypes.c_uint32)]
+
+
 class SnapshotInfo(ctypes.Structure):
     """hrt_snapshot_info: what an accumulator must be created with to take a snapshot blob."""
     _fields_ = [(n, ctypes.c_uint32) for n in ("version", "flags", "width", "height", "n_tiles", "uniform")] + \
@@ -182,7 +189,8 @@ OPTIONAL = {"hrt_abi_version", "hrt_last_launch", "hrt_debug_box_test", "hrt_sce
             "hrt_accum_resolve_filtered", "hrt_accum_resolve_filtered_host", "hrt_debug_filter",
         "hrt_accum_add_features", "hrt_accum_feature_samples", "hrt_accum_features", "hrt_accum_features_host",
             "hrt_accum_resolve_guided", "hrt_accum_resolve_guided_host", "hrt_debug_guided", "hrt_debug_accum_features",
-            "hrt_accum_snapshot", "hrt_accum_restore", "hrt_accum_snapshot_info", "hrt_accum_merge_tiles"}
+            "hrt_accum_snapshot", "hrt_accum_restore", "hrt_accum_snapshot_info", "hrt_accum_merge_tiles",
+            "hrt_accum_resolve_guided_ex", "hrt_accum_resolve_guided_ex_host", "hrt_debug_guided_ex"}
 HRT_LIB_OVERRIDE = bool(os.environ.get("HRT_LIB"))
 
 # Every entry point of include/hrt/hrt.h (tests/test_abi.py checks the header against this list).
@@ -206,6 +214,7 @@ EXPORTS = [
     "hrt_accum_add_features", "hrt_accum_feature_samples", "hrt_accum_features", "hrt_accum_features_host",
     "hrt_accum_resolve_guided", "hrt_accum_resolve_guided_host", "hrt_debug_guided", "hrt_debug_accum_features",
     "hrt_accum_snapshot", "hrt_accum_restore", "hrt_accum_snapshot_info", "hrt_accum_merge_tiles",
+    "hrt_accum_resolve_guided_ex", "hrt_accum_resolve_guided_ex_host", "hrt_debug_guided_ex",
 ]
 
 ABI_VERSION = 6  # include/hrt/hrt.h HRT_ABI_VERSION: the struct layouts below
@@ -320,6 +329,9 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "hrt_accum_restore": (S, [vp, vp, u64]),
         "hrt_accum_snapshot_info": (S, [vp, u64, ctypes.POINTER(SnapshotInfo), vp, u32]),
         "hrt_accum_merge_tiles": (S, [vp, vp, vp]),
+        "hrt_accum_resolve_guided_ex": (S, [vp, ctypes.POINTER(GuidedExParams), i32, vp, vp]),
+        "hrt_accum_resolve_guided_ex_host": (S, [vp, ctypes.POINTER(GuidedExParams), i32, vp]),
+        "hrt_debug_guided_ex": (S, [i32, vp, vp, vp, u32, u32, u32, f, f, f, f, u32, f, vp]),
     }
     for name, (res, args) in sig.items():
         if name in OPTIONAL and HRT_LIB_OVERRIDE and not hasattr(L, name):
@@ -614,6 +626,28 @@ def guided_params(iterations: int = 3, sigma: float = 4.0, normal: Optional[floa
     return GuidedParams(int(iterations), float(sigma), float(t[0]), float(t[1]), float(t[2]))
 
 
+GUIDED_DEMODULATE = 1  # hrt_guided_ex_params.flags
+# demodulate=True: the albedo floor and the tolerances under demodulation (the sweep and the rule
+# of GUIDED_DEFAULTS; the remodulated texture carries the albedo plane's own sampling noise, so the normal term is tighter)
+DEMOD_FLOOR = 0.01
+DEMOD_DEFAULTS = dict(normal=0.05, albedo=0.2, depth=0.2)
+
+
+def _demod_floor(demodulate) -> float:
+    return DEMOD_FLOOR if demodulate is True else float(demodulate)
+
+
+def guided_ex_params(iterations: int = 3, sigma: float = 4.0, normal: Optional[float] = None, albedo: Optional[float] = None,
+                     depth: Optional[float] = None, demodulate=True) -> GuidedExParams:
+    """hrt_guided_ex_params.  demodulate: True means DEMOD_FLOOR, a float is the albedo floor; the tolerances default to
+    DEMOD_DEFAULTS.  False: flags 0 and GUIDED_DEFAULTS, which is hrt_guided_params' frame."""
+    on = demodulate is not False and demodulate is not None
+    dflt = DEMOD_DEFAULTS if on else GUIDED_DEFAULTS
+    t = [dflt[k] if v is None else v for k, v in (("normal", normal), ("albedo", albedo), ("depth", depth))]
+    return GuidedExParams(int(iterations), float(sigma), float(t[0]), float(t[1]), float(t[2]), GUIDED_DEMODULATE if on else 0,
+                          _demod_floor(demodulate) if on else 0.0, 0)
+
+
 class Accumulator:
     """hrt_accum: device-resident raw per-pixel sums of a tile set (the whole frame when `tiles` is None).  Passes
     add sample ranges (`add` with params.sample_offset / params.samples), and `resolve` gives the frame of the
@@ -806,12 +840,19 @@ class Accumulator:
         _check(load().hrt_accum_resolve_filtered_host(self.h, ctypes.byref(f), _ACCUM_FORMATS[fmt], out.ctypes.data))
         return self._shaped(out)
 
-    def resolve_guided(self, fmt: str = "f32", denoise=None, guide=True) -> np.ndarray:
+    def resolve_guided(self, fmt: str = "f32", denoise=None, guide=True, demodulate=False) -> np.ndarray:
         """resolve(fmt, denoise) through the filter WITH the feature terms (hrt_accum_resolve_guided_host), for a
         noise=True, features=True accumulator that holds feature samples.  denoise: as resolve's, None meaning True.
-        guide: True means GUIDED_DEFAULTS, a dict(normal=, albedo=, depth=) overrides a tolerance (0: that term off)."""
+        guide: True means GUIDED_DEFAULTS, a dict(normal=, albedo=, depth=) overrides a tolerance (0: that term off).
+        demodulate (opt-in, hrt_accum_resolve_guided_ex_host with HRT_GUIDED_DEMODULATE): filter the radiance divided
+        by the first-hit albedo and multiply it back; True means the floor DEMOD_FLOOR, a float is the albedo floor,
+        and guide=True then means DEMOD_DEFAULTS."""
         out = np.zeros(self.n_pixels * 4, np.float32 if fmt == "f32" else np.uint8)
         kw = {} if denoise is None or denoise is True else dict(denoise)
+        if demodulate is not False and demodulate is not None:
+            g = guided_ex_params(**kw, **({} if guide is True else dict(guide)), demodulate=demodulate)
+            _check(load().hrt_accum_resolve_guided_ex_host(self.h, ctypes.byref(g), _ACCUM_FORMATS[fmt], out.ctypes.data))
+            return self._shaped(out)
         g = guided_params(**kw, **({} if guide is True else dict(guide)))
         _check(load().hrt_accum_resolve_guided_host(self.h, ctypes.byref(g), _ACCUM_FORMATS[fmt], out.ctypes.data))
         return self._shaped(out)
@@ -957,14 +998,21 @@ def debug_filter(raster: np.ndarray, iterations: int, sigma: float, on_device: b
 
 
 def debug_guided(raster: np.ndarray, albedo: np.ndarray, normal: np.ndarray, iterations: int, sigma: float, kn: float = 0.0,
-                 ka: float = 0.0, kz: float = 0.0, on_device: bool = False) -> np.ndarray:
+                 ka: float = 0.0, kz: float = 0.0, on_device: bool = False, demodulate=False) -> np.ndarray:
     """hrt_debug_guided: debug_filter for the guided filter (csrc/filter.h).  albedo, normal: the feature rasters,
-    (height, width, 4) float32 ((a.xyz, -), (n.xyz, z)); kn, ka, kz: 1 / tolerance of each term, 0: off."""
+    (height, width, 4) float32 ((a.xyz, -), (n.xyz, z)); kn, ka, kz: 1 / tolerance of each term, 0: off.
+    demodulate (hrt_debug_guided_ex with HRT_GUIDED_DEMODULATE; True: DEMOD_FLOOR, a float: the albedo floor): the
+    raster is gather's (c, v), and (c'' before the sqrt, v' in demodulated units) comes back."""
     r = np.ascontiguousarray(raster, np.float32)
     a, n = np.ascontiguousarray(albedo, np.float32), np.ascontiguousarray(normal, np.float32)
     if r.ndim != 3 or r.shape[2] != 4 or a.shape != r.shape or n.shape != r.shape:
         raise ValueError("raster, albedo and normal must be (height, width, 4) float32 of one shape")
     out = np.zeros_like(r)
+    if demodulate is not False and demodulate is not None:
+        _check(load().hrt_debug_guided_ex(1 if on_device else 0, r.ctypes.data, a.ctypes.data, n.ctypes.data, r.shape[1], r.shape[0],
+                                          int(iterations), float(sigma), float(kn), float(ka), float(kz), GUIDED_DEMODULATE,
+                                          _demod_floor(demodulate), out.ctypes.data))
+        return out
     _check(load().hrt_debug_guided(1 if on_device else 0, r.ctypes.data, a.ctypes.data, n.ctypes.data, r.shape[1], r.shape[0],
                                    int(iterations), float(sigma), float(kn), float(ka), float(kz), out.ctypes.data))
     return out

@@ -533,12 +533,52 @@ hrt_status hrt_accum_resolve_guided(hrt_accum* a, const hrt_guided_params* g, in
 /* ... into HOST memory; waits for the device as hrt_accum_resolve_host does */
 hrt_status hrt_accum_resolve_guided_host(hrt_accum* a, const hrt_guided_params* g, int32_t format, void* out);
 
+/* ---- guided resolve with options: demodulation by the first-hit albedo ----
+ * hrt_accum_resolve_guided with a flags word.  With flags == 0 the frame, the preconditions and every status are
+ * hrt_accum_resolve_guided's, bit for bit (and with all three tolerances 0 as well, hrt_accum_resolve_filtered's).
+ * HRT_GUIDED_DEMODULATE: the filter runs on the radiance DIVIDED by the first-hit albedo and the albedo is multiplied
+ * back afterwards, so the filter averages irradiance across texture edges and the texture returns at full sharpness.
+ * An opt-in, never a default (README.md, DESIGN.md section 6.10 say where it helps and where it does not).
+ * THE BIT CONTRACT of the demodulated frame (csrc/filter.h; f32, -ffp-contract=off, IEEE '/'), for a pixel p, with a_p
+ * the xyz of the mean albedo plane (exactly the bits hrt_accum_features returns) and floor = albedo_floor:
+ *   1. Divisor: m_p = (at_least(a_p.x, floor), at_least(a_p.y, floor), at_least(a_p.z, floor)), at_least(x, lo) being
+ *      x > lo ? x : lo, so a NaN albedo gives floor.
+ *   2. Demodulated input, in place of the guided frame's (c_p, v_p): d_p = (c_p.x / m_p.x, c_p.y / m_p.y, c_p.z / m_p.z);
+ *      l = (c_p.x + c_p.y) + c_p.z and l' the same of d_p; g = l > 0 ? l' / l : 0.0f; v'_p = v_p * (g * g).  This keeps
+ *      the relative standard error of the luminance and is exact for a grey albedo.
+ *   3. Iterations: exactly the guided frame's on the planes (d, v'): the same order, prefilter, r, taps, H, sv and sw;
+ *      the enabled feature terms are unchanged and read the same mean planes.
+ *   4. Output: c'' = (d'.x * m_p.x, d'.y * m_p.y, d'.z * m_p.z) of the last iteration's d', then sqrtf per channel and
+ *      alpha 1, or the PPM rule on that.  The sw == 0 escape returns the demodulated input pixel, which is remodulated
+ *      like any other.
+ * The demodulated frame is a function of the sums, m2, (N, K) per tile, the feature planes, the floor and the covered
+ * pixel set: it does not depend on the tile cut, and the resolve writes none of its inputs.  With the flag set and all
+ * three tolerances 0 the frame is the demodulated variance-only filter, a legal setting.  The option is a parameter of
+ * a resolve, not state: a snapshot does not carry it.  No pass over the frame and no raster is added to the guided
+ * resolve's.
+ * Errors, each changing nothing: hrt_accum_resolve_guided's, and HRT_ERR_INVALID_ARG for unknown flag bits, for
+ * reserved != 0, and for an albedo_floor that is <= 0 or NaN while HRT_GUIDED_DEMODULATE is set (the floor is not
+ * read when it is clear). */
+enum { HRT_GUIDED_DEMODULATE = 1 };
+typedef struct hrt_guided_ex_params hrt_guided_ex_params;
+struct hrt_guided_ex_params { /* 32 bytes */
+  uint32_t iterations;         /* as hrt_guided_params */
+  float sigma;                 /* as hrt_guided_params */
+  float normal, albedo, depth; /* as hrt_guided_params */
+  uint32_t flags;              /* HRT_GUIDED_* bits; others: HRT_ERR_INVALID_ARG */
+  float albedo_floor;          /* HRT_GUIDED_DEMODULATE: > 0; 0.01 is a good start */
+  uint32_t reserved;           /* 0 */
+};
+hrt_status hrt_accum_resolve_guided_ex(hrt_accum* a, const hrt_guided_ex_params* g, int32_t format, void* d_out, void* stream);
+/* ... into HOST memory; waits for the device as hrt_accum_resolve_host does */
+hrt_status hrt_accum_resolve_guided_ex_host(hrt_accum* a, const hrt_guided_ex_params* g, int32_t format, void* out);
+
 /* ---- snapshots: checkpoint, restore and transport of the WHOLE accumulator state ----
  * hrt_accum_snapshot writes everything the accumulator's later answers depend on into one self-describing blob in host
  * memory; hrt_accum_restore puts it into an empty accumulator created with the same width, height, tile list and flags
  * (on the same committed scene, as hrt_accum_upload requires; the blob carries no scene fingerprint).
  * THE RESTORE CONTRACT: after a restore every later call returns the bits, and the status, it would have returned on the
- * snapshotted accumulator: resolve, resolve_filtered, resolve_guided, noise, tile_samples, samples, feature_samples,
+ * snapshotted accumulator: resolve, resolve_filtered, resolve_guided, resolve_guided_ex, noise, tile_samples, samples, feature_samples,
  * features, and every later add, add_tiles, add_features and merge* with its acceptance or refusal.  So "render S1,
  * snapshot, destroy, create, restore, render S2" equals "render S1, render S2" bit for bit in every plane.  The filters'
  * raster buffers are scratch and are not part of a snapshot.
@@ -735,6 +775,13 @@ hrt_status hrt_debug_filter(int32_t on_device, const float* raster, uint32_t wid
  * (0: off; negative or NaN: HRT_ERR_INVALID_ARG). */
 hrt_status hrt_debug_guided(int32_t on_device, const float* raster, const float* albedo, const float* normal, uint32_t width,
                             uint32_t height, uint32_t iterations, float sigma, float kn, float ka, float kz, float* out);
+/* hrt_debug_guided with hrt_guided_ex_params' flags and albedo_floor (the same checks).  With HRT_GUIDED_DEMODULATE
+ * the raster is already gather's (c, v): steps 2 to 4 of the demodulated frame's contract run on it, the divisor from
+ * the albedo raster, and out is (c''.xyz BEFORE the sqrt, v' in demodulated units); an absent pixel comes out as it
+ * went in.  flags == 0: hrt_debug_guided. */
+hrt_status hrt_debug_guided_ex(int32_t on_device, const float* raster, const float* albedo, const float* normal, uint32_t width,
+                               uint32_t height, uint32_t iterations, float sigma, float kn, float ka, float kz, uint32_t flags,
+                               float albedo_floor, float* out);
 /* The raw feature sums (fa, fn) of a HRT_ACCUM_FEATURES accumulator (n_pixels x 4 f32 each, packed as the tiles are)
  * into host memory, after a device synchronisation: for the tests that hold the planes to their bit contract. */
 hrt_status hrt_debug_accum_features(hrt_accum* a, float* fa_out, float* fn_out);
