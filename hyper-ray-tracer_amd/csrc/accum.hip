@@ -16,6 +16,7 @@
 #include "feature_pass.h"
 #include "filter.h"
 #include "render_host.h"
+#include "tile_reduce.h"
 
 using namespace hrt;
 using namespace hrt::lane;
@@ -168,28 +169,7 @@ __global__ __launch_bounds__(accum::NOISE_BLOCK) void accum_noise(const float4* 
     s = s + e;
     m = accum::larger(m, e);
   }
-  sh_s[j] = s;
-  sh_m[j] = m;
-  __syncthreads();
-  if (j < 128u) { /* s = 128, across waves */
-    s = s + sh_s[j + 128u];
-    m = accum::larger(m, sh_m[j + 128u]);
-  }
-  __syncthreads();
-  if (j < 128u) {
-    sh_s[j] = s;
-    sh_m[j] = m;
-  }
-  __syncthreads();
-  if (j < 64u) { /* s = 64 across waves, then 32 ... 1 inside wave 0: lane j takes lane j + s's value */
-    s = s + sh_s[j + 64u];
-    m = accum::larger(m, sh_m[j + 64u]);
-    for (int off = 32; off >= 1; off >>= 1) {
-      s = s + __shfl_down(s, off);
-      m = accum::larger(m, __shfl_down(m, off));
-    }
-    if (j == 0u) out[blockIdx.x] = make_float2(s * (1.0f / (float)T.n), m);
-  }
+  accum::tile_reduce_block(s, m, T.n, sh_s, sh_m, out + blockIdx.x);
 }
 
 template <int FORMAT>
@@ -311,6 +291,9 @@ struct hrt_accum {
   uint32_t feat_blocks = 0, feat_log_bw = 0;
   /* the guided resolve's two mean feature rasters over the planes' bounding box, made by the first guided resolve */
   float4* d_gplane[2] = {nullptr, nullptr};
+  /* hrt_accum_noise_filtered's packed per-pixel errs when the caller keeps none (n_px f32), made by the first such call;
+   * scratch like the rasters: not part of a snapshot */
+  float* d_ferr = nullptr;
   /* hrt_accum_merge_tiles' table of the selected tiles, made by the first such merge, and its host copy */
   MergeTile* d_mtiles = nullptr;
   std::vector<MergeTile> h_mtiles;
@@ -468,9 +451,9 @@ void filter_gather_plane(hrt_accum* a, const filter::Demod& demod, hipStream_t s
 }
 /* the filtered resolve, or with the terms K the guided one: the colour plane gathered, the feature rasters if guided,
  * then the iterations.  demod (a guided resolve's option, filter.h): the plane is gathered demodulated and the last
- * iteration remodulates */
+ * iteration remodulates.  format filter::FORMAT_ERR: d_out takes the filtered noise estimate against err_floor */
 void launch_filtered(hrt_accum* a, uint32_t iterations, float sigma, const filter::Terms* K, const filter::Demod& demod, int32_t format,
-                     void* d_out, hipStream_t stream) {
+                     void* d_out, hipStream_t stream, float err_floor = 0.0f) {
   filter_gather_plane(a, K ? demod : NO_DEMOD, stream);
   const uint32_t nt = (uint32_t)a->tiles.size();
   if (K && !a->d_gplane[0]) { /* the two feature rasters, once: a present pixel's features are written by every resolve */
@@ -488,7 +471,7 @@ void launch_filtered(hrt_accum* a, uint32_t iterations, float sigma, const filte
     filter::launch_gather_features(a->d_fa, a->d_fn, a->d_ftiles, nt, a->f_blocks, 1.0f / (float)feature_samples(a), albedo, normal,
                                    a->f_w, stream);
   filter::launch_atrous(a->d_fplane[0], a->d_fplane[1], albedo, normal, a->f_w, a->f_h, a->d_ftiles, nt, a->f_blocks, iterations, sigma,
-                        K ? *K : filter::Terms{}, K ? demod : NO_DEMOD, format, d_out, stream);
+                        K ? *K : filter::Terms{}, K ? demod : NO_DEMOD, format, d_out, stream, err_floor);
 }
 
 /* hrt_accum_resolve_guided's checks beyond the filtered resolve's, and its tolerances as filter.h takes them */
@@ -735,7 +718,8 @@ void hrt_accum_destroy(hrt_accum* a) {
   for (float4* plane : a->d_fplane)
     if (plane) (void)hipFree(plane);
   if (a->d_ftiles) (void)hipFree(a->d_ftiles);
-  for (void* p : {(void*)a->d_fa, (void*)a->d_fn, (void*)a->d_feat_tiles, (void*)a->d_gplane[0], (void*)a->d_gplane[1], (void*)a->d_mtiles})
+  for (void* p : {(void*)a->d_fa, (void*)a->d_fn, (void*)a->d_feat_tiles, (void*)a->d_gplane[0], (void*)a->d_gplane[1], (void*)a->d_mtiles,
+                  (void*)a->d_ferr})
     if (p) (void)hipFree(p);
   if (prev >= 0) (void)hipSetDevice(prev);
   delete a;
@@ -984,6 +968,40 @@ hrt_status hrt_accum_resolve_guided_ex_host(hrt_accum* a, const hrt_guided_ex_pa
     guided_state(a);
     resolve_to_host(a, format, out, "hipMemcpy(guided resolve)",
                     [&](void* d_out) { launch_filtered(a, g->iterations, g->sigma, &K, demod, format, d_out, nullptr); });
+  });
+}
+
+hrt_status hrt_accum_noise_filtered(hrt_accum* a, const hrt_guided_ex_params* g, float floor, float* d_err, void* stream_,
+                                    hrt_tile_noise* tiles_out) {
+  return hguard([&] {
+    if (!a || !g || !tiles_out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_noise_filtered: null argument"};
+    if (!(floor > 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_noise_filtered: floor must be > 0"};
+    filter::Demod demod = NO_DEMOD;
+    const filter::Terms K = guided_ex_args(g, demod);
+    /* no term and no flag: the variance-only filter, which reads no feature plane and asks for none */
+    const bool plain = !demod.on && K.kn == 0.0f && K.ka == 0.0f && K.kz == 0.0f;
+    if (plain) filter_state(a);
+    else guided_state(a);
+    DeviceGuard dg(a->device);
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!d_err) {
+      filter_prepare(a, stream); /* the refusal of overlapping tiles comes before anything is made */
+      if (!a->d_ferr) hip_check(hipMalloc((void**)&a->d_ferr, a->n_px * sizeof(float)), "hipMalloc(filtered noise plane)");
+      d_err = a->d_ferr;
+    }
+    const uint32_t nt = (uint32_t)a->tiles.size();
+    launch_filtered(a, g->iterations, g->sigma, plain ? nullptr : &K, demod, filter::FORMAT_ERR, d_err, stream, floor);
+    filter::launch_err_reduce(d_err, a->d_ftiles, nt, a->d_nout, stream);
+    std::vector<float2> rec(nt);
+    hip_check(hipMemcpyAsync(rec.data(), a->d_nout, nt * sizeof(float2), hipMemcpyDeviceToHost, stream),
+              "hipMemcpyAsync(filtered noise records)");
+    hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize(filtered noise)");
+    for (uint32_t t = 0; t < nt; t++) {
+      tiles_out[t].mean = rec[t].x;
+      tiles_out[t].max = rec[t].y;
+      tiles_out[t].samples = a->ledger.samples(t);
+      tiles_out[t].chunks = a->ledger.chunks(t);
+    }
   });
 }
 
@@ -1345,6 +1363,69 @@ hrt_status hrt_debug_guided_ex(int32_t on_device, const float* raster, const flo
     if (!(kn >= 0.0f) || !(ka >= 0.0f) || !(kz >= 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_guided_ex: a negative or NaN term"};
     const filter::Demod demod = guided_ex_option(flags, albedo_floor);
     debug_atrous(on_device, raster, albedo, normal, width, height, iterations, sigma, filter::Terms{kn, ka, kz}, demod, out);
+  });
+}
+
+hrt_status hrt_debug_noise_filtered(int32_t on_device, const float* raster, const float* albedo, const float* normal, uint32_t width,
+                                    uint32_t height, uint32_t iterations, float sigma, float kn, float ka, float kz, uint32_t flags,
+                                    float albedo_floor, float floor, const hrt_tile* tiles, uint32_t n_tiles, float* err_out,
+                                    float* mean_max_out) {
+  return hguard([&] {
+    if (!raster || !tiles || n_tiles == 0 || !err_out || !mean_max_out || width == 0 || height == 0 || width > 65535 || height > 65535)
+      throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_noise_filtered: null argument, no tiles, or a width or height outside [1, 65535]"};
+    const hrt_filter_params f{iterations, sigma};
+    filter_args(&f);
+    if (!(kn >= 0.0f) || !(ka >= 0.0f) || !(kz >= 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_noise_filtered: a negative or NaN term"};
+    const filter::Demod demod = guided_ex_option(flags, albedo_floor);
+    if (!(floor > 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_noise_filtered: floor must be > 0"};
+    const bool plain = !demod.on && kn == 0.0f && ka == 0.0f && kz == 0.0f;
+    if (!plain && (!albedo || !normal)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_noise_filtered: a term or the flag needs the feature rasters"};
+    /* the tiles lie inside the raster, overlap nowhere and cover present pixels only */
+    const size_t area = (size_t)width * height;
+    std::vector<bool> covered(area, false);
+    std::vector<filter::FilterTile> ft(n_tiles);
+    size_t off = 0, blocks = 0;
+    for (uint32_t t = 0; t < n_tiles; t++) {
+      const hrt_tile& T = tiles[t];
+      if (T.w == 0 || T.h == 0 || T.x >= width || T.y >= height || T.w > width - T.x || T.h > height - T.y)
+        throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_noise_filtered: a tile is empty or leaves the raster"};
+      for (uint32_t y = T.y; y < T.y + T.h; y++)
+        for (uint32_t x = T.x; x < T.x + T.w; x++) {
+          const size_t k = (size_t)y * width + x;
+          if (covered[k] || raster[4 * k + 3] < 0.0f)
+            throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_noise_filtered: tiles overlap or cover an absent pixel"};
+          covered[k] = true;
+        }
+      ft[t] = filter::FilterTile{T.x, T.y, T.w, T.h, (uint32_t)off, (uint32_t)blocks, 0.0f, 0.0f};
+      off += (size_t)T.w * T.h;
+      blocks += filter::tile_blocks(T.w, T.h);
+    }
+    const filter::Terms K{kn, ka, kz};
+    const float* al = plain ? nullptr : albedo;
+    const float* no = plain ? nullptr : normal;
+    if (!on_device) {
+      std::vector<float> out(4 * area), err(area);
+      filter::filter_raster(raster, al, no, width, height, iterations, sigma, K, demod, out.data(), err.data(), floor);
+      for (uint32_t t = 0; t < n_tiles; t++) {
+        const filter::FilterTile& T = ft[t];
+        for (uint32_t y = 0; y < T.h; y++)
+          for (uint32_t x = 0; x < T.w; x++) err_out[(size_t)T.off + (size_t)y * T.w + x] = err[(size_t)(T.y + y) * width + (T.x + x)];
+        accum::tile_reduce(err_out + T.off, T.w * T.h, mean_max_out[2 * t], mean_max_out[2 * t + 1]);
+      }
+      return;
+    }
+    /* the real kernels on the calling thread's current device */
+    const size_t bytes = area * sizeof(float4);
+    DevBuf<float4> d_a(bytes, raster), d_b(bytes), d_al(al ? bytes : 0, al), d_no(no ? bytes : 0, no);
+    DevBuf<float> d_err(off * sizeof(float));
+    DevBuf<float2> d_rec(n_tiles * sizeof(float2));
+    DevBuf<filter::FilterTile> d_tiles(n_tiles * sizeof(filter::FilterTile), ft.data());
+    if (demod.on) filter::launch_demodulate(d_a.p, d_al.p, area, demod.floor, nullptr);
+    filter::launch_atrous(d_a.p, d_b.p, al ? d_al.p : nullptr, no ? d_no.p : nullptr, width, height, d_tiles.p, n_tiles, (uint32_t)blocks,
+                          iterations, sigma, K, demod, filter::FORMAT_ERR, d_err.p, nullptr, floor);
+    filter::launch_err_reduce(d_err.p, d_tiles.p, n_tiles, d_rec.p, nullptr);
+    hip_check(hipMemcpy(err_out, d_err.p, off * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy");
+    hip_check(hipMemcpy(mean_max_out, d_rec.p, n_tiles * sizeof(float2), hipMemcpyDeviceToHost), "hipMemcpy");
   });
 }
 

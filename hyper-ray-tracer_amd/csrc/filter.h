@@ -50,6 +50,16 @@
  *      output rule above on c''; the sw == 0 escape's pixel is remodulated like any other.  v' stays in demodulated
  *      units.
  * Without the flag none of this runs and floor is not read: the frame is the guided one bit for bit.
+ *
+ * The bits of the FILTERED NOISE ESTIMATE (hrt_accum_noise_filtered; hrt_debug_noise_filtered): the relative standard
+ * error of the filtered frame's pixel as the filter itself propagates it.  With (c', v') pixel p's output of the LAST
+ * iteration of any of the three filters above, the sw == 0 escape's pixel included, and `floor` the caller's (> 0):
+ *   plain and guided (filtered_err): l' = luma(c'); err = sqrtf(v') / at_least(l', floor);
+ *   demodulated (filtered_err_demod), the last iteration giving d' and v' in demodulated units: c'' = remodulate(d', m_p),
+ *     l_d = luma(d'), l'' = luma(c''), gr = l_d > 0 ? l'' / l_d : 0.0f, v'' = v' * (gr * gr), then filtered_err of
+ *     (c'', v''): the mirror of demodulate's step 2.
+ * The last iteration writes err, packed, where a frame pixel would have gone (FORMAT_ERR); the frame is never written.
+ * A tile's mean and max are accum::tile_reduce of its packed errs, the reduction of hrt_accum_noise.
  */
 #pragma once
 #include <stddef.h>
@@ -100,6 +110,14 @@ HRT_HD Px demodulate(const Px& p, Vec3 m) {
   return d;
 }
 HRT_HD Vec3 remodulate(Vec3 d, Vec3 m) { return v3(d.x * m.x, d.y * m.y, d.z * m.z); }
+/* the filtered noise estimate of a last iteration's pixel; the demodulated form takes the pixel before remodulation */
+HRT_HD float filtered_err(Vec3 c, float v, float floor) { return sqrtf(v) / accum::at_least(accum::luma(c), floor); }
+HRT_HD float filtered_err_demod(Vec3 d, float v, Vec3 m, float floor) {
+  const Vec3 c = remodulate(d, m);
+  const float ld = accum::luma(d), l = accum::luma(c);
+  const float gr = ld > 0.0f ? l / ld : 0.0f;
+  return filtered_err(c, v * (gr * gr), floor);
+}
 /* the option of a guided resolve: off, or on with the caller's albedo floor (> 0; not read when off) */
 struct Demod {
   bool on;
@@ -205,9 +223,11 @@ HRT_HD Vec3 resolve(const Px& p) { return v3(sqrtf(p.c.x), sqrtf(p.c.y), sqrtf(p
  * through as they are.  albedo and normal: the two feature rasters (a.xyz, -) and (n.xyz, z) of the guided filter, read
  * at present pixels only, or both null: the plain filter (K is not read).  demod.on (the guided filter only): `in` is
  * gather's (c, v); its present pixels are demodulated before the first iteration and the last one's colour is
- * remodulated, so out is (c''.xyz, v' in demodulated units). */
+ * remodulated, so out is (c''.xyz, v' in demodulated units).  err (or null): width x height f32, the filtered noise
+ * estimate of every present pixel against err_floor, 0 at an absent one. */
 inline void filter_raster(const float* in, const float* albedo, const float* normal, uint32_t width, uint32_t height,
-                          uint32_t iterations, float sigma, const Terms& K, const Demod& demod, float* out) {
+                          uint32_t iterations, float sigma, const Terms& K, const Demod& demod, float* out, float* err = nullptr,
+                          float err_floor = 0.0f) {
   const size_t n = (size_t)width * height;
   std::vector<float> a(in, in + 4 * n), b(4 * n);
   auto divisor = [=](size_t k) { return demod_divisor(v3(albedo[k], albedo[k + 1], albedo[k + 2]), demod.floor); };
@@ -244,6 +264,12 @@ inline void filter_raster(const float* in, const float* albedo, const float* nor
       }
     a.swap(b);
   }
+  if (err)
+    for (size_t k = 0; k < 4 * n; k += 4) {
+      const Vec3 c = v3(a[k], a[k + 1], a[k + 2]);
+      if (!present(px(c.x, c.y, c.z, a[k + 3]))) err[k / 4] = 0.0f;
+      else err[k / 4] = demod.on ? filtered_err_demod(c, a[k + 3], divisor(k), err_floor) : filtered_err(c, a[k + 3], err_floor);
+    }
   if (demod.on)
     for (size_t k = 0; k < 4 * n; k += 4) {
       if (!present(px(a[k], a[k + 1], a[k + 2], a[k + 3]))) continue;
@@ -267,8 +293,9 @@ struct alignas(16) FilterTile {
 };
 inline uint32_t tile_blocks(uint32_t w, uint32_t h) { return ((w + BLOCK_W - 1) / BLOCK_W) * ((h + BLOCK_H - 1) / BLOCK_H); }
 
-/* format of the last iteration's packed output: HRT_ACCUM_F32, HRT_ACCUM_RGBA8, or RAW: float4 (c', v') */
-constexpr int32_t FORMAT_RAW = -1;
+/* format of the last iteration's packed output: HRT_ACCUM_F32, HRT_ACCUM_RGBA8, RAW: float4 (c', v'), or ERR: one f32,
+ * the filtered noise estimate against launch_atrous' err_floor */
+constexpr int32_t FORMAT_RAW = -1, FORMAT_ERR = -3;
 
 /* acc, m2 (packed) -> plane (plane_w x plane_h float4) at the tiles' pixels */
 void launch_gather(const void* d_acc, const float* d_m2, const FilterTile* d_tiles, uint32_t n_tiles, uint32_t n_blocks,
@@ -285,10 +312,13 @@ void launch_gather_features(const void* d_fa, const void* d_fn, const FilterTile
                             float inv, void* d_albedo, void* d_normal, uint32_t plane_w, void* stream);
 /* `iterations` of the filter from plane a (b is the other plane; both are written), the last one to d_out packed.
  * d_albedo and d_normal: the guided filter's feature rasters, or both null: the plain filter (K is not read).
- * demod.on (the guided filter only): plane a is demodulated, and the last iteration remodulates what it writes. */
+ * demod.on (the guided filter only): plane a is demodulated, and the last iteration remodulates what it writes.
+ * err_floor is read for FORMAT_ERR alone. */
 void launch_atrous(void* d_a, void* d_b, const void* d_albedo, const void* d_normal, uint32_t plane_w, uint32_t plane_h,
                    const FilterTile* d_tiles, uint32_t n_tiles, uint32_t n_blocks, uint32_t iterations, float sigma, const Terms& K,
-                   const Demod& demod, int32_t format, void* d_out, void* stream);
+                   const Demod& demod, int32_t format, void* d_out, void* stream, float err_floor = 0.0f);
+/* the packed errs of every tile reduced to its (mean, max): accum.h tile_reduce, one workgroup per tile */
+void launch_err_reduce(const float* d_err, const FilterTile* d_tiles, uint32_t n_tiles, void* d_mean_max, void* stream);
 
 }  // namespace filter
 }  // namespace hrt

@@ -18,6 +18,9 @@
  *                   and its LAST iteration multiplies the albedo of the centre pixel (at hand for the feature terms, in
  *                   LDS when the features are staged) back where the packed output is written.  The inner iterations are
  *                   guided_atrous itself.  demod_raster does the gather's part for a raster of hrt_debug_guided_ex.
+ *   filter_atrous_err, guided_atrous_err   the LAST iteration of hrt_accum_noise_filtered: the same body, which writes
+ *                   the filtered noise estimate (filter.h filtered_err), packed f32, and no frame.
+ *   filter_err_reduce   the packed errs -> each tile's (mean, max), accum_noise's reduction (tile_reduce.h).
  *
  * LDS layout: rows of (32 + 4 * step) float4, linear.  A wave is two block rows of 32 lanes; a tap is the same offset
  * for every lane, so each 16-lane group of a 16-byte LDS read (lanes {0-3, 12-15, 20-27} etc.) reads 16 distinct
@@ -31,6 +34,7 @@
 #include "feature_pass.h"
 #include "filter.h"
 #include "kernel_common.h"
+#include "tile_reduce.h"
 
 using namespace hrt;
 using namespace hrt::filter;
@@ -152,12 +156,13 @@ struct DemodPlanes : FeaturePlanes {
 /* One iteration, the body of both kernels.  sh: the workgroup's LDS.
  * STEP: the step staged in LDS, or 0: taps from global memory with the step in `step`.
  * FORMAT: -2: an inner iteration over the plane's blocks, to the plane `out`; else the last one over the tiles'
- * blocks, to the packed `out` as FORMAT_RAW, HRT_ACCUM_F32 or HRT_ACCUM_RGBA8. */
+ * blocks, to the packed `out` as FORMAT_RAW, HRT_ACCUM_F32 or HRT_ACCUM_RGBA8, or as FORMAT_ERR: the filtered noise
+ * estimate against err_floor (filter.h), one f32 where the frame's pixel would have gone; the frame is not written. */
 constexpr int32_t FORMAT_PLANE = -2;
 template <int STEP, int32_t FORMAT, class Features>
 __device__ __forceinline__ void atrous_iteration(float4* sh, const Features F, const float4* __restrict__ in, uint32_t plane_w,
                                                  uint32_t plane_h, const FilterTile* __restrict__ tiles, uint32_t n_tiles, int step,
-                                                 float sigma, void* __restrict__ out) {
+                                                 float sigma, void* __restrict__ out, float err_floor = 0.0f) {
   constexpr int HALO = 2 * STEP, RW = (int)BLOCK_W + 2 * HALO, RH = (int)BLOCK_H + 2 * HALO;
   /* the block's corner on the plane, the pixels of it this launch owns, and where a packed result goes */
   uint32_t x0, y0, own_w, own_h, row_w = 0;
@@ -218,6 +223,7 @@ __device__ __forceinline__ void atrous_iteration(float4* sh, const Features F, c
   };
   const Px p = at(x, y);
   Px o;
+  [[maybe_unused]] float err = 0.0f;
   if constexpr (Features::guided) {
     /* one call site for both sources of the features, so that atrous_pixel is inlined (a wave-uniform branch per tap) */
     auto feat = [=](int qx, int qy) {
@@ -231,16 +237,25 @@ __device__ __forceinline__ void atrous_iteration(float4* sh, const Features F, c
     o = present(p) ? atrous_pixel(at, feature_terms(feat, x, y, F.K), x, y, s, sigma) : p;
     if constexpr (Features::demod) {
       /* the centre's albedo is the one the feature terms hold already */
-      if (present(p)) o.c = remodulate(o.c, demod_divisor(feat(x, y).a, F.floor));
+      if constexpr (FORMAT == FORMAT_ERR) {
+        if (present(p)) err = filtered_err_demod(o.c, o.v, demod_divisor(feat(x, y).a, F.floor), err_floor);
+      } else {
+        if (present(p)) o.c = remodulate(o.c, demod_divisor(feat(x, y).a, F.floor));
+      }
+    } else if constexpr (FORMAT == FORMAT_ERR) {
+      err = filtered_err(o.c, o.v, err_floor);
     }
   } else {
     o = present(p) ? atrous_pixel(at, NoFeatures{}, x, y, s, sigma) : p;
+    if constexpr (FORMAT == FORMAT_ERR) err = filtered_err(o.c, o.v, err_floor);
   }
   if constexpr (FORMAT == FORMAT_PLANE) {
     static_cast<float4*>(out)[(size_t)(y + cy) * plane_w + (size_t)(x + cx)] = as_f4(o);
   } else {
     const size_t i = packed0 + (size_t)ty * row_w + (size_t)tx;
-    if constexpr (FORMAT == FORMAT_RAW) {
+    if constexpr (FORMAT == FORMAT_ERR) {
+      static_cast<float*>(out)[i] = err;
+    } else if constexpr (FORMAT == FORMAT_RAW) {
       static_cast<float4*>(out)[i] = as_f4(o);
     } else {
       const Vec3 d = resolve(o);
@@ -281,6 +296,45 @@ __global__ __launch_bounds__(BLOCK) void guided_atrous_demod(const float4* __res
                                  step, sigma, out);
 }
 
+/* The last iteration as the filtered noise estimate (FORMAT_ERR): kernels of their own, so that the frame formats'
+ * kernels keep their arguments and their code.  DEMOD: the last iteration of a demodulated resolve. */
+template <int STEP>
+__global__ __launch_bounds__(BLOCK) void filter_atrous_err(const float4* __restrict__ in, uint32_t plane_w, uint32_t plane_h,
+                                                           const FilterTile* __restrict__ tiles, uint32_t n_tiles, int step,
+                                                           float sigma, float err_floor, float* __restrict__ out) {
+  __shared__ float4 sh[STEP ? lds_bytes(STEP, 1) / sizeof(float4) : 1];
+  atrous_iteration<STEP, FORMAT_ERR>(sh, NoPlanes{}, in, plane_w, plane_h, tiles, n_tiles, step, sigma, out, err_floor);
+}
+template <int STEP, bool DEMOD>
+__global__ __launch_bounds__(BLOCK) void guided_atrous_err(const float4* __restrict__ in, const float4* __restrict__ albedo,
+                                                           const float4* __restrict__ normal, uint32_t plane_w, uint32_t plane_h,
+                                                           const FilterTile* __restrict__ tiles, uint32_t n_tiles, int step,
+                                                           float sigma, Terms K, uint32_t feat_lds, float albedo_floor,
+                                                           float err_floor, float* __restrict__ out) {
+  extern __shared__ float4 sh_planes[];
+  if constexpr (DEMOD)
+    atrous_iteration<STEP, FORMAT_ERR>(sh_planes, DemodPlanes{{albedo, normal, K, feat_lds}, albedo_floor}, in, plane_w, plane_h, tiles,
+                                       n_tiles, step, sigma, out, err_floor);
+  else
+    atrous_iteration<STEP, FORMAT_ERR>(sh_planes, FeaturePlanes{albedo, normal, K, feat_lds}, in, plane_w, plane_h, tiles, n_tiles, step,
+                                       sigma, out, err_floor);
+}
+
+/* The tile reduce of the packed errs: one workgroup per tile, accum_noise's fold and tree (tile_reduce.h) */
+__global__ __launch_bounds__(accum::NOISE_BLOCK) void filter_err_reduce(const float* __restrict__ err, const FilterTile* __restrict__ tiles,
+                                                                        float2* __restrict__ out) {
+  __shared__ float sh_s[accum::NOISE_BLOCK], sh_m[accum::NOISE_BLOCK];
+  const FilterTile T = tiles[blockIdx.x];
+  const uint32_t n = T.w * T.h;
+  float s = 0.0f, m = 0.0f;
+  for (uint32_t k = threadIdx.x; k < n; k += accum::NOISE_BLOCK) {
+    const float e = err[(size_t)T.off + k];
+    s = s + e;
+    m = accum::larger(m, e);
+  }
+  accum::tile_reduce_block(s, m, n, sh_s, sh_m, out + blockIdx.x);
+}
+
 /* one iteration's launch; albedo and normal null: the plain filter; demod.on: the last iteration of a demodulated one */
 struct Iteration {
   const float4 *in, *albedo, *normal;
@@ -293,11 +347,31 @@ struct Iteration {
   void* out;
   hipStream_t stream;
   Demod demod;
+  float err_floor; /* FORMAT_ERR */
 };
 
+/* the last iteration as the filtered noise estimate */
+template <int STEP>
+void launch_err(const Iteration& I, bool feat_lds) {
+  if (!I.albedo) {
+    hipLaunchKernelGGL((filter_atrous_err<STEP>), dim3(I.blocks), dim3(BLOCK), 0, I.stream, I.in, I.w, I.h, I.tiles, I.n_tiles, I.step,
+                       I.sigma, I.err_floor, (float*)I.out);
+    hip_check(hipGetLastError(), "filter_atrous_err launch");
+  } else if constexpr (STEP <= GUIDED_STAGED_MAX) {
+    const size_t lds = lds_bytes(STEP, feat_lds ? 3 : 1);
+    if (I.demod.on)
+      hipLaunchKernelGGL((guided_atrous_err<STEP, true>), dim3(I.blocks), dim3(BLOCK), lds, I.stream, I.in, I.albedo, I.normal, I.w, I.h,
+                         I.tiles, I.n_tiles, I.step, I.sigma, I.K, feat_lds ? 1u : 0u, I.demod.floor, I.err_floor, (float*)I.out);
+    else
+      hipLaunchKernelGGL((guided_atrous_err<STEP, false>), dim3(I.blocks), dim3(BLOCK), lds, I.stream, I.in, I.albedo, I.normal, I.w, I.h,
+                         I.tiles, I.n_tiles, I.step, I.sigma, I.K, feat_lds ? 1u : 0u, 0.0f, I.err_floor, (float*)I.out);
+    hip_check(hipGetLastError(), "guided_atrous_err launch");
+  }
+}
 template <int STEP, int32_t FORMAT>
 void launch_one(const Iteration& I, bool feat_lds) {
-  if (!I.albedo) {
+  if constexpr (FORMAT == FORMAT_ERR) return launch_err<STEP>(I, feat_lds);
+  else if (!I.albedo) {
     hipLaunchKernelGGL((filter_atrous<STEP, FORMAT>), dim3(I.blocks), dim3(BLOCK), 0, I.stream, I.in, I.w, I.h, I.tiles, I.n_tiles,
                        I.step, I.sigma, I.out);
     hip_check(hipGetLastError(), "filter_atrous launch");
@@ -365,11 +439,11 @@ void launch_gather_features(const void* d_fa, const void* d_fn, const FilterTile
 
 void launch_atrous(void* d_a, void* d_b, const void* d_albedo, const void* d_normal, uint32_t plane_w, uint32_t plane_h,
                    const FilterTile* d_tiles, uint32_t n_tiles, uint32_t n_blocks, uint32_t iterations, float sigma, const Terms& K,
-                   const Demod& demod, int32_t format, void* d_out, void* stream) {
+                   const Demod& demod, int32_t format, void* d_out, void* stream, float err_floor) {
   const uint32_t plane_blocks = ((plane_w + BLOCK_W - 1) / BLOCK_W) * ((plane_h + BLOCK_H - 1) / BLOCK_H);
   float4 *src = (float4*)d_a, *dst = (float4*)d_b;
   Iteration I{src, (const float4*)d_albedo, (const float4*)d_normal, plane_w, plane_h, d_tiles, n_tiles, plane_blocks, 1, sigma, K, dst,
-              (hipStream_t)stream, Demod{false, 0.0f}};
+              (hipStream_t)stream, Demod{false, 0.0f}, err_floor};
   for (uint32_t i = 0; i + 1 < iterations; i++) {
     I.in = src, I.out = dst, I.step = 1 << i;
     launch_step<FORMAT_PLANE>(I);
@@ -377,9 +451,15 @@ void launch_atrous(void* d_a, void* d_b, const void* d_albedo, const void* d_nor
   }
   I.in = src, I.out = d_out, I.step = 1 << (iterations - 1), I.blocks = n_blocks;
   if (d_albedo) I.demod = demod; /* the last iteration remodulates */
-  if (format == FORMAT_RAW) launch_step<FORMAT_RAW>(I);
+  if (format == FORMAT_ERR) launch_step<FORMAT_ERR>(I);
+  else if (format == FORMAT_RAW) launch_step<FORMAT_RAW>(I);
   else if (format == HRT_ACCUM_F32) launch_step<HRT_ACCUM_F32>(I);
   else launch_step<HRT_ACCUM_RGBA8>(I);
+}
+
+void launch_err_reduce(const float* d_err, const FilterTile* d_tiles, uint32_t n_tiles, void* d_mean_max, void* stream) {
+  hipLaunchKernelGGL(filter_err_reduce, dim3(n_tiles), dim3(accum::NOISE_BLOCK), 0, (hipStream_t)stream, d_err, d_tiles, (float2*)d_mean_max);
+  hip_check(hipGetLastError(), "filter_err_reduce launch");
 }
 
 }  // namespace filter

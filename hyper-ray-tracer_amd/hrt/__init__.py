@@ -190,7 +190,8 @@ OPTIONAL = {"hrt_abi_version", "hrt_last_launch", "hrt_debug_box_test", "hrt_sce
         "hrt_accum_add_features", "hrt_accum_feature_samples", "hrt_accum_features", "hrt_accum_features_host",
             "hrt_accum_resolve_guided", "hrt_accum_resolve_guided_host", "hrt_debug_guided", "hrt_debug_accum_features",
             "hrt_accum_snapshot", "hrt_accum_restore", "hrt_accum_snapshot_info", "hrt_accum_merge_tiles",
-            "hrt_accum_resolve_guided_ex", "hrt_accum_resolve_guided_ex_host", "hrt_debug_guided_ex"}
+            "hrt_accum_resolve_guided_ex", "hrt_accum_resolve_guided_ex_host", "hrt_debug_guided_ex",
+            "hrt_accum_noise_filtered", "hrt_debug_noise_filtered"}
 HRT_LIB_OVERRIDE = bool(os.environ.get("HRT_LIB"))
 
 # Every entry point of include/hrt/hrt.h (tests/test_abi.py checks the header against this list).
@@ -215,6 +216,7 @@ EXPORTS = [
     "hrt_accum_resolve_guided", "hrt_accum_resolve_guided_host", "hrt_debug_guided", "hrt_debug_accum_features",
     "hrt_accum_snapshot", "hrt_accum_restore", "hrt_accum_snapshot_info", "hrt_accum_merge_tiles",
     "hrt_accum_resolve_guided_ex", "hrt_accum_resolve_guided_ex_host", "hrt_debug_guided_ex",
+    "hrt_accum_noise_filtered", "hrt_debug_noise_filtered",
 ]
 
 ABI_VERSION = 6  # include/hrt/hrt.h HRT_ABI_VERSION: the struct layouts below
@@ -332,6 +334,8 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "hrt_accum_resolve_guided_ex": (S, [vp, ctypes.POINTER(GuidedExParams), i32, vp, vp]),
         "hrt_accum_resolve_guided_ex_host": (S, [vp, ctypes.POINTER(GuidedExParams), i32, vp]),
         "hrt_debug_guided_ex": (S, [i32, vp, vp, vp, u32, u32, u32, f, f, f, f, u32, f, vp]),
+        "hrt_accum_noise_filtered": (S, [vp, ctypes.POINTER(GuidedExParams), f, vp, vp, vp]),
+        "hrt_debug_noise_filtered": (S, [i32, vp, vp, vp, u32, u32, u32, f, f, f, f, u32, f, f, vp, u32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         if name in OPTIONAL and HRT_LIB_OVERRIDE and not hasattr(L, name):
@@ -802,6 +806,85 @@ class Accumulator:
             if not todo:
                 return rec
 
+    def _noise_filtered_params(self, denoise, guide, demodulate) -> GuidedExParams:
+        kw = {} if denoise is None or denoise is True else dict(denoise)
+        demod = demodulate is not False and demodulate is not None
+        if guide is False or guide is None:
+            terms = dict(normal=0.0, albedo=0.0, depth=0.0)
+        else:
+            terms = {} if guide is True else dict(guide)
+        return guided_ex_params(**kw, **terms, demodulate=demodulate if demod else False)
+
+    def noise_filtered(self, floor: float = 0.05, denoise=True, guide=False, demodulate=False, error_map: bool = False):
+        """hrt_accum_noise_filtered: `noise` for the frame a filtered resolve shows, from the variance the filter itself
+        propagates (the variance of the filtered frame, not its blur: a lower bound on the shown frame's error).
+        denoise, guide, demodulate: resolve_guided's conventions, naming the resolve whose frame is estimated;
+        guide=False (the default) switches every feature term off, which with demodulate=False is resolve(denoise=...)'s
+        frame and needs no feature planes.  Returns what `noise` returns."""
+        g = self._noise_filtered_params(denoise, guide, demodulate)
+        rec = (TileNoise * len(self.tiles))()
+        if not error_map:
+            _check(load().hrt_accum_noise_filtered(self.h, ctypes.byref(g), float(floor), None, None, ctypes.cast(rec, ctypes.c_void_p)))
+            return list(rec)
+        import torch
+
+        dev = torch.device("cuda", self.scene.device if self.scene.device >= 0 else torch.cuda.current_device())
+        buf = torch.empty(self.n_pixels, dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        _check(load().hrt_accum_noise_filtered(self.h, ctypes.byref(g), float(floor), ctypes.c_void_p(buf.data_ptr()),
+                                               ctypes.c_void_p(stream.cuda_stream), ctypes.cast(rec, ctypes.c_void_p)))
+        return list(rec), buf.cpu().numpy()
+
+    def refine_filtered(self, cam: Camera, p: RenderParams, target: float, pass_spp: int, max_spp: int, floor: float = 0.05,
+                        denoise=True, guide=False, demodulate=False, min_spp: int = 0, on_pass=None, resume: bool = False):
+        """refine, with the tiles selected on noise_filtered(floor, denoise, guide, demodulate): the passes stop when the
+        FILTERED preview's estimated error meets the target.  The loop and the pass-numbering rule are refine's (a tile's
+        k-th pass is samples [k * pass_spp, (k + 1) * pass_spp); resume=True goes on from whatever the tiles hold), except
+        that a tile which met the target may be selected again when its neighbours' passes move its estimate.  While
+        any tile holds fewer than 2 chunks the filtered estimate does not exist (HRT_ERR_STATE); that round uses
+        noise(floor), whose +inf keeps those tiles selected.  With guide or demodulate the feature samples must be held
+        already (add_features): it raises otherwise, before any pass."""
+        needs_features = (guide is not False and guide is not None) or (demodulate is not False and demodulate is not None)
+        if needs_features and (not self.has_features or self.feature_samples == 0):
+            raise ValueError("refine_filtered with guide or demodulate needs feature samples (add_features) before the first pass")
+
+        def estimate():
+            try:
+                return self.noise_filtered(floor, denoise, guide, demodulate)
+            except HrtError as e:
+                if e.status != ERR_STATE:
+                    raise
+                return self.noise(floor)  # a tile with fewer than 2 chunks: its +inf keeps it selected
+
+        q = RenderParams.from_buffer_copy(p)
+        q.samples = int(pass_spp)
+        held = self.tile_samples
+        rec = None
+        if not (resume and any(held)):
+            if len(set(held)) != 1:
+                raise ValueError("refine_filtered starts from an accumulator whose tiles hold the same passes")
+            q.sample_offset = held[0]
+            self.add(cam, q)
+            rec = estimate()
+            if on_pass is not None:
+                on_pass(list(range(len(self.tiles))), rec)
+        while True:
+            # A tile's filtered record moves with its neighbours' passes, so the selection is made among ALL tiles after
+            # every pass, and the next pass goes to the selected tiles that hold the fewest samples: what happens next is a
+            # function of what the tiles hold, which is what makes an interrupted run resumable.
+            if rec is None:
+                rec = estimate()
+            todo = [t for t in range(len(self.tiles)) if (rec[t].mean > target or rec[t].samples < min_spp) and rec[t].samples < max_spp]
+            if not todo:
+                return rec
+            count = min(rec[t].samples for t in todo)
+            group = [t for t in todo if rec[t].samples == count]
+            q.sample_offset = count
+            self.add(cam, q, tiles=group)
+            rec = estimate()
+            if on_pass is not None:
+                on_pass(group, rec)
+
     def add_features(self, cam: Camera, p: RenderParams):
         """The first-hit features of samples [p.sample_offset, p.sample_offset + p.samples) of every pixel, added to the
         feature planes (hrt_accum_add_features): one launch, no radiance."""
@@ -1016,6 +1099,27 @@ def debug_guided(raster: np.ndarray, albedo: np.ndarray, normal: np.ndarray, ite
     _check(load().hrt_debug_guided(1 if on_device else 0, r.ctypes.data, a.ctypes.data, n.ctypes.data, r.shape[1], r.shape[0],
                                    int(iterations), float(sigma), float(kn), float(ka), float(kz), out.ctypes.data))
     return out
+
+
+def debug_noise_filtered(raster: np.ndarray, albedo, normal, iterations: int, sigma: float, tiles, kn: float = 0.0, ka: float = 0.0,
+                         kz: float = 0.0, demodulate=False, floor: float = 0.05, on_device: bool = False):
+    """hrt_debug_noise_filtered: hrt_accum_noise_filtered's arithmetic (csrc/filter.h) on a raster cut into `tiles`
+    ((x, y, w, h) inside the raster, disjoint, present pixels only).  albedo, normal: the feature rasters, or None when
+    no term and no demodulation is on.  Returns (err, mean_max): the errs packed as the tiles are and (n_tiles, 2)."""
+    r = np.ascontiguousarray(raster, np.float32)
+    a = None if albedo is None else np.ascontiguousarray(albedo, np.float32)
+    n = None if normal is None else np.ascontiguousarray(normal, np.float32)
+    tl = [tuple(int(v) for v in t) for t in tiles]
+    arr = (Tile * max(1, len(tl)))(*[Tile(*t) for t in tl])
+    err = np.zeros(sum(t[2] * t[3] for t in tl), np.float32)
+    mm = np.zeros((len(tl), 2), np.float32)
+    on = demodulate is not False and demodulate is not None
+    _check(load().hrt_debug_noise_filtered(1 if on_device else 0, r.ctypes.data, None if a is None else a.ctypes.data,
+                                           None if n is None else n.ctypes.data, r.shape[1], r.shape[0], int(iterations), float(sigma),
+                                           float(kn), float(ka), float(kz), GUIDED_DEMODULATE if on else 0,
+                                           _demod_floor(demodulate) if on else 0.0, float(floor), ctypes.cast(arr, ctypes.c_void_p),
+                                           len(tl), err.ctypes.data, mm.ctypes.data))
+    return err, mm
 
 
 def debug_accum_features(acc: "Accumulator"):

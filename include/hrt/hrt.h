@@ -573,6 +573,47 @@ hrt_status hrt_accum_resolve_guided_ex(hrt_accum* a, const hrt_guided_ex_params*
 /* ... into HOST memory; waits for the device as hrt_accum_resolve_host does */
 hrt_status hrt_accum_resolve_guided_ex_host(hrt_accum* a, const hrt_guided_ex_params* g, int32_t format, void* out);
 
+/* ---- noise estimate of the FILTERED frame ----
+ * hrt_accum_noise for the frame a filtered resolve shows: every a-trous iteration carries the variance of the filtered
+ * mean, v' = sv / (sw * sw), and this call turns the last iteration's into a per-pixel relative standard error and
+ * per-tile records, so that a caller who looks at the filtered preview can stop refining on ITS error (Python
+ * Accumulator.refine_filtered, examples/render_adaptive_filtered.c).  g is exactly hrt_accum_resolve_guided_ex's
+ * parameter block and names the resolve whose frame is estimated; all tolerances 0 and flags 0 is
+ * hrt_accum_resolve_filtered's frame.  No frame is written and no pass is added: the iterations are the resolve's own,
+ * the last one writing the error where the frame's pixel would have gone, then one reduce the size of hrt_accum_noise's.
+ * THE BIT CONTRACT (csrc/filter.h; f32, -ffp-contract=off, IEEE '/' and sqrtf).  Let (c', v') be pixel p's output of the
+ * LAST iteration of the resolve g describes; the iterations are those of the contracts above, unchanged:
+ *   - flags == 0: l' = (c'.x + c'.y) + c'.z; err = sqrtf(v') / at_least(l', floor);
+ *   - HRT_GUIDED_DEMODULATE: the last iteration yields d' and v' in demodulated units and c'' = (d'.x * m_p.x, d'.y *
+ *     m_p.y, d'.z * m_p.z) (step 4 above); l_d = (d'.x + d'.y) + d'.z and l'' the same of c''; gr = l_d > 0 ? l'' / l_d
+ *     : 0.0f; v'' = v' * (gr * gr); err = sqrtf(v'') / at_least(l'', floor): the mirror of step 2 above;
+ *   - the sw == 0 escape yields the input pixel's (c, v) and goes through the same expression;
+ *   - a tile's mean and max are exactly hrt_accum_noise's reduction over the tile's packed errs: thread j of 256 folds
+ *     pixels j, j + 256, ... in order from 0, then x[j] = x[j] (op) x[j + s] for s = 128 ... 1, mean = x[0] * (1.0f /
+ *     (float)pixels); NaN and +inf propagate as they do there.
+ * The per-pixel err is a function of the sums, m2, (N, K) per tile, the feature planes, g, floor and the covered pixel
+ * set: it does not depend on the tile cut.  UNLIKE hrt_accum_noise, a tile's record DOES depend on its neighbours'
+ * passes, because the filter's footprint crosses tile edges.  The call writes none of its inputs (the rasters and the
+ * error plane it uses are scratch, not part of a snapshot): every later call returns the bits and the status it would
+ * have returned without it.
+ * WHAT IT IS AND IS NOT: v' propagates the input variances through the tap weights as if the taps were independent and
+ * the weights fixed.  It estimates the VARIANCE of the filtered frame, not its bias (blur): texture or geometry smaller
+ * than the footprint is averaged away and this estimate does not see it.  So err is a lower bound on the shown frame's
+ * error, tightest where the filter's assumptions hold (README.md and DESIGN.md section 6.11 give the calibration).  An
+ * opt-in policy input, never a default.
+ * d_err: device memory, n_pixels floats packed as the tiles are, or NULL (the accumulator then keeps the plane itself,
+ * 4 B per pixel, made by the first such call and freed with it).  tiles_out: host memory, n_tiles records; samples and
+ * chunks are the tile's N and K, as in hrt_accum_noise.  Synchronises `stream`, as hrt_accum_noise does.
+ * Errors, each changing nothing: every precondition and status of hrt_accum_resolve_guided_ex, except that the feature
+ * planes (HRT_ACCUM_FEATURES) and feature samples are required only when a tolerance is > 0 or the flag is set:
+ * hrt_accum_resolve_guided_ex refuses an accumulator without HRT_ACCUM_FEATURES even at all-zero tolerances, while this
+ * call takes the all-off case through the variance-only filter (the same bits), whose preconditions are
+ * hrt_accum_resolve_filtered's, so a HRT_ACCUM_NOISE-only accumulator is accepted.  In particular a tile with fewer than
+ * 2 chunks is HRT_ERR_STATE (hrt_accum_noise answers +inf for it).  HRT_ERR_INVALID_ARG for floor <= 0 or NaN and for a
+ * null g or tiles_out. */
+hrt_status hrt_accum_noise_filtered(hrt_accum* a, const hrt_guided_ex_params* g, float floor, float* d_err, void* stream,
+                                    hrt_tile_noise* tiles_out);
+
 /* ---- snapshots: checkpoint, restore and transport of the WHOLE accumulator state ----
  * hrt_accum_snapshot writes everything the accumulator's later answers depend on into one self-describing blob in host
  * memory; hrt_accum_restore puts it into an empty accumulator created with the same width, height, tile list and flags
@@ -782,6 +823,16 @@ hrt_status hrt_debug_guided(int32_t on_device, const float* raster, const float*
 hrt_status hrt_debug_guided_ex(int32_t on_device, const float* raster, const float* albedo, const float* normal, uint32_t width,
                                uint32_t height, uint32_t iterations, float sigma, float kn, float ka, float kz, uint32_t flags,
                                float albedo_floor, float* out);
+/* hrt_accum_noise_filtered's arithmetic on a raster the caller gives (hrt_debug_guided_ex's arguments and checks; the
+ * raster is gather's (c, v)), cut into `tiles`, which lie inside the raster, do not overlap and cover present pixels
+ * only (HRT_ERR_INVALID_ARG otherwise): on the DEVICE through the real last-iteration and reduce kernels (on_device = 1)
+ * or with the same arithmetic on the host (0).  err_out takes the errs packed as the tiles are (the sum of w * h
+ * floats), mean_max_out n_tiles x (mean, max).  floor as hrt_accum_noise_filtered's.  With kn = ka = kz = 0 and
+ * flags == 0 the feature rasters are not read and may be NULL. */
+hrt_status hrt_debug_noise_filtered(int32_t on_device, const float* raster, const float* albedo, const float* normal, uint32_t width,
+                                    uint32_t height, uint32_t iterations, float sigma, float kn, float ka, float kz, uint32_t flags,
+                                    float albedo_floor, float floor, const hrt_tile* tiles, uint32_t n_tiles, float* err_out,
+                                    float* mean_max_out);
 /* The raw feature sums (fa, fn) of a HRT_ACCUM_FEATURES accumulator (n_pixels x 4 f32 each, packed as the tiles are)
  * into host memory, after a device synchronisation: for the tests that hold the planes to their bit contract. */
 hrt_status hrt_debug_accum_features(hrt_accum* a, float* fa_out, float* fn_out);
