@@ -1027,7 +1027,9 @@ HRT_LANE_FI void sphere_uv(Vec3 p, float& u, float& v) {
 
 /* Record of the winning leaf in world space (hit_record.rs, sphere.rs:57-73, rect.rs:70-83,
  * constant_medium.rs:66-75, then translation.rs:33-35 / rotation.rs:119-132 on the way out). */
-template <bool FULL>
+/* UV: (u, v) always (csrc/query.h: a hit record for a caller); a render computes a sphere's only under a texture that
+ * reads them (Mat.needs_uv) */
+template <bool FULL, bool UV = false>
 HRT_LANE Rec make_record(const KParams& P, uint32_t winner, float t, Vec3 wo, Vec3 wd, float time, float tau) {
   Rec rec;
   rec.u = 0.0f;
@@ -1045,6 +1047,7 @@ HRT_LANE Rec make_record(const KParams& P, uint32_t winner, float t, Vec3 wo, Ve
     rec.mat = km >> 4;
     Vec3 at = wo + t * wd;
     Vec3 outward = (at - c) / p0.w;
+    if constexpr (UV) sphere_uv(outward, rec.u, rec.v);
     rec.p = at;
     set_face_normal(rec, wd, outward);
     return rec;
@@ -1067,7 +1070,7 @@ HRT_LANE Rec make_record(const KParams& P, uint32_t winner, float t, Vec3 wo, Ve
       const uint32_t km = pp->km;
       const uint32_t pkind = km & 3u;
       rec.mat = km >> 4;
-      const bool uv = P.mats[rec.mat].needs_uv != 0;
+      const bool uv = UV || P.mats[rec.mat].needs_uv != 0;
       float4 p0 = ld4(pp->p0);
       if (pkind == G::P_RECT) {
         int k, a, b;

@@ -882,6 +882,8 @@ void hrt::chunk_schedule(const hrt_scene* s, const hrt_render_params* p, uint32_
                s->opts.chunk_max, s->opts.chunk_uniform ? 0u : 32u, chunk, n_head, first, n_tail);
 }
 
+void hrt::check_render_params(const hrt_camera* cam, const hrt_render_params* p) { check_render_args(cam, p); }
+
 /* The kernel parameters of a feature pass (features.hip reads the scene from global memory: nothing is staged) and
  * the instantiation the plan names, as hrt_debug_trace_path picks its own.  Approximate plans are refused. */
 KParams hrt::feature_params(hrt_scene* s, const hrt_camera* cam, const hrt_render_params* p, int& cull, bool& full) {

@@ -86,6 +86,11 @@ void render_launch(hrt_scene* s, const hrt_camera* cam, const hrt_render_params*
 /* render.hip: the kernel parameters of a feature pass over samples [p->sample_offset, + p->samples) and the
  * instantiation its plan names (cull: layout.h CULL_EXACT or CULL_REFERENCE); an approximate plan is HRT_ERR_UNSUPPORTED */
 lane::KParams feature_params(hrt_scene* s, const hrt_camera* cam, const hrt_render_params* p, int& cull, bool& full);
+/* render.hip: the knobs in effect now and at the scene's commit, into the thread's launch record (hrt_last_launch);
+ * called right after resident_grid has written that record */
+void launch_knobs(const hrt_scene* s);
+/* render.hip: the checks every kernel entry point makes on (cam, p) (check_render_args), for query.hip */
+void check_render_params(const hrt_camera* cam, const hrt_render_params* p);
 /* render.hip: a render's sample chunks (lane.h frame_chunks) */
 void chunk_schedule(const hrt_scene* s, const hrt_render_params* p, uint32_t& chunk, uint32_t& n_head, uint32_t& first,
                     uint32_t& n_tail);

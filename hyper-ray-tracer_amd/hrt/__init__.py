@@ -178,6 +178,21 @@ class SceneOptions(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint32) for n in ("bvh_ties", "walk_tree", "chunk_min", "chunk_max", "chunk_uniform")]
 
 
+class QueryParams(ctypes.Structure):
+    """hrt_query_params (24 bytes): flags, the interval the rays' times lie in, the seed of the media's draws."""
+    _fields_ = [("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("time0", ctypes.c_float), ("time1", ctypes.c_float),
+                ("seed", ctypes.c_uint64)]
+
+
+# hrt_ray / hrt_hit (48 bytes each) as numpy structured types
+RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("t_min", np.float32), ("direction", np.float32, 3), ("t_max", np.float32),
+                      ("time", np.float32), ("pixel", np.uint32), ("sample", np.uint32), ("segment", np.uint32)])
+HIT_DTYPE = np.dtype([("t", np.float32), ("prim", np.uint32), ("material", np.uint32), ("flags", np.uint32),
+                      ("point", np.float32, 3), ("u", np.float32), ("normal", np.float32, 3), ("v", np.float32)])
+HIT_HIT, HIT_FRONT, HIT_MEDIUM, HIT_INVALID = 1, 2, 4, 8
+QUERY_SKIP_MEDIA, QUERY_NO_LDS, QUERY_REFERENCE_CULL = 1, 2, 4
+
+
 # Diagnostics an older build may lack; only tolerated when HRT_LIB points at another build (A/B runs)
 OPTIONAL = {"hrt_abi_version", "hrt_last_launch", "hrt_debug_box_test", "hrt_scene_set_options", "hrt_scene_get_options",
             "hrt_debug_sample_chunks", "hrt_scene_set_view",
@@ -191,7 +206,8 @@ OPTIONAL = {"hrt_abi_version", "hrt_last_launch", "hrt_debug_box_test", "hrt_sce
             "hrt_accum_resolve_guided", "hrt_accum_resolve_guided_host", "hrt_debug_guided", "hrt_debug_accum_features",
             "hrt_accum_snapshot", "hrt_accum_restore", "hrt_accum_snapshot_info", "hrt_accum_merge_tiles",
             "hrt_accum_resolve_guided_ex", "hrt_accum_resolve_guided_ex_host", "hrt_debug_guided_ex",
-            "hrt_accum_noise_filtered", "hrt_debug_noise_filtered"}
+            "hrt_accum_noise_filtered", "hrt_debug_noise_filtered",
+            "hrt_scene_intersect", "hrt_scene_intersect_host", "hrt_camera_rays", "hrt_camera_rays_host"}
 HRT_LIB_OVERRIDE = bool(os.environ.get("HRT_LIB"))
 
 # Every entry point of include/hrt/hrt.h (tests/test_abi.py checks the header against this list).
@@ -217,6 +233,7 @@ EXPORTS = [
     "hrt_accum_snapshot", "hrt_accum_restore", "hrt_accum_snapshot_info", "hrt_accum_merge_tiles",
     "hrt_accum_resolve_guided_ex", "hrt_accum_resolve_guided_ex_host", "hrt_debug_guided_ex",
     "hrt_accum_noise_filtered", "hrt_debug_noise_filtered",
+    "hrt_scene_intersect", "hrt_scene_intersect_host", "hrt_camera_rays", "hrt_camera_rays_host",
 ]
 
 ABI_VERSION = 6  # include/hrt/hrt.h HRT_ABI_VERSION: the struct layouts below
@@ -336,6 +353,10 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "hrt_debug_guided_ex": (S, [i32, vp, vp, vp, u32, u32, u32, f, f, f, f, u32, f, vp]),
         "hrt_accum_noise_filtered": (S, [vp, ctypes.POINTER(GuidedExParams), f, vp, vp, vp]),
         "hrt_debug_noise_filtered": (S, [i32, vp, vp, vp, u32, u32, u32, f, f, f, f, u32, f, f, vp, u32, vp, vp]),
+        "hrt_scene_intersect": (S, [vp, ctypes.POINTER(QueryParams), vp, u64, vp, vp]),
+        "hrt_scene_intersect_host": (S, [vp, ctypes.POINTER(QueryParams), vp, u64, vp]),
+        "hrt_camera_rays": (S, [vp, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams), vp, u32, vp, vp]),
+        "hrt_camera_rays_host": (S, [vp, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams), vp, u32, vp]),
     }
     for name, (res, args) in sig.items():
         if name in OPTIONAL and HRT_LIB_OVERRIDE and not hasattr(L, name):
@@ -504,6 +525,32 @@ class Scene:
         buf = ctypes.create_string_buffer(bytes(data), len(data))
         _check(load().hrt_debug_poke_blob(self.h, offset, buf, len(data)))
 
+    def intersect(self, rays, flags: int = 0, seed: int = 0, shutter=(0.0, 1.0), out=None, stream: int = 0):
+        """The closest hit of every ray (hrt_scene_intersect).  A numpy array of RAY_DTYPE goes through the host variant
+        and returns an array of HIT_DTYPE; a CUDA torch tensor (n x 12 float32 words, or n x 48 bytes) goes through the
+        device variant on `stream` and returns an (n, 12) float32 tensor of hit records (view it as int32 for the ids).
+        shutter: the interval the rays' times lie in; seed: the key of the media's draws (with each ray's pixel, sample
+        and segment)."""
+        q = query_params(flags, seed, shutter)
+        if isinstance(rays, np.ndarray):
+            rays = np.ascontiguousarray(rays, RAY_DTYPE)
+            hits = np.empty(rays.shape, HIT_DTYPE) if out is None else out
+            if hits.dtype != HIT_DTYPE or hits.shape != rays.shape or not hits.flags.c_contiguous:
+                raise ValueError("out: a contiguous HIT_DTYPE array of the rays' shape")
+            _check(load().hrt_scene_intersect_host(self.h, ctypes.byref(q), rays.ctypes.data, rays.size, hits.ctypes.data))
+            return hits
+        import torch
+
+        if not (isinstance(rays, torch.Tensor) and rays.is_cuda and rays.is_contiguous() and
+                rays.numel() * rays.element_size() % 48 == 0):
+            raise ValueError("rays: a numpy RAY_DTYPE array or a contiguous CUDA tensor of 48-byte records")
+        n = rays.numel() * rays.element_size() // 48
+        hits = torch.empty((n, 12), dtype=torch.float32, device=rays.device) if out is None else out
+        if not (hits.is_cuda and hits.is_contiguous() and hits.numel() * hits.element_size() == 48 * n):
+            raise ValueError("out: a contiguous CUDA tensor of n 48-byte records")
+        _check(load().hrt_scene_intersect(self.h, ctypes.byref(q), rays.data_ptr(), n, hits.data_ptr(), stream or None))
+        return hits
+
     def scene_info(self) -> SceneInfo:
         si = SceneInfo()
         _check(load().hrt_scene_get_info(self.h, ctypes.byref(si)))
@@ -578,6 +625,29 @@ def params(width, height, samples, max_depth=50, seed=1, background=(0.7, 0.8, 1
     for i in range(3):
         p.background[i] = float(background[i])
     return p
+
+
+def query_params(flags: int = 0, seed: int = 0, shutter=(0.0, 1.0)) -> QueryParams:
+    """hrt_query_params: QUERY_* flags, the seed of the media's draws, the interval the rays' times lie in."""
+    return QueryParams(flags, 0, float(shutter[0]), float(shutter[1]), seed)
+
+
+def camera_rays(scene: "Scene", cam: Camera, p: RenderParams, tiles=None, device: bool = False, stream: int = 0):
+    """The camera rays of samples [p.sample_offset, + p.samples) of every pixel of `tiles` (default: the frame as one
+    tile), ray (packed pixel) * p.samples + k (hrt_camera_rays): a RAY_DTYPE array, or with device=True an (n, 12)
+    float32 CUDA tensor on the current torch device (which must be the scene's)."""
+    tiles = [(0, 0, p.width, p.height)] if tiles is None else list(tiles)
+    arr = (Tile * len(tiles))(*[Tile(*t) for t in tiles])
+    n = sum(t[2] * t[3] for t in tiles) * p.samples
+    if not device:
+        rays = np.empty(n, RAY_DTYPE)
+        _check(load().hrt_camera_rays_host(scene.h, ctypes.byref(cam), ctypes.byref(p), arr, len(tiles), rays.ctypes.data))
+        return rays
+    import torch
+
+    rays = torch.empty((n, 12), dtype=torch.float32, device="cuda")
+    _check(load().hrt_camera_rays(scene.h, ctypes.byref(cam), ctypes.byref(p), arr, len(tiles), rays.data_ptr(), stream or None))
+    return rays
 
 
 def tile_grid(width: int, height: int, tile_size: int = 80, rank: int = 0, world: int = 1) -> List[Tuple[int, int, int, int]]:

@@ -688,6 +688,97 @@ hrt_status hrt_accum_snapshot_info(const void* blob, uint64_t size, hrt_snapshot
  * call time. */
 hrt_status hrt_accum_merge_tiles(hrt_accum* dst, const hrt_accum* src, void* stream);
 
+/* ---- ray queries: the closest hits of caller-supplied rays ----
+ * Everything above starts at a pixel.  hrt_scene_intersect answers "what does this ray hit?" for rays the caller
+ * keeps in device memory: picking, autofocus (examples/render_autofocus.c), visibility between two points, baking, a
+ * depth map from another camera model, the segments of a path replayed.  hrt_camera_rays writes the camera rays a
+ * render's samples start with, so the two together are a frame's first hits.
+ *
+ * THE BIT CONTRACT of a hit (csrc/query.h, -ffp-contract=off, all in f32):
+ *   Closest hit.  Ray i's answer is the closest hit of world.hit(ray, t_min, t_max) as a render's segment with that
+ *   origin, direction and time computes it: the walk the feature pass makes (lane.h trace over the reference node
+ *   stream from t_min, the closest starting at t_max), then the hit record (lane.h make_record; hit_record.rs).  The
+ *   interval is the reference's at both ends: a root t is refused when t < t_min or t_max < t (sphere.rs:53-55,
+ *   moving_sphere.rs:74-76, rect.rs:61), so t == t_min and t == t_max are both accepted, and a later primitive
+ *   replaces an earlier one at an equal t.  The direction is used as given (t is in units of its length).
+ *   Culling.  Boxes are culled by the scene's exact mode (the reference's box test plus culling that provably drops
+ *   no accepted hit) when [time0, time1] of the params lies inside the interval the scene's BVH boxes were built for,
+ *   and by the reference's test alone otherwise or under HRT_QUERY_REFERENCE_CULL.  Both give the same hits; there is
+ *   no approximate mode for queries.
+ *   The record.  t, point, normal, u, v and the front-face bit are the hit record's; the normal faces the ray.  u and
+ *   v are ALWAYS computed (a render computes a sphere's only under an image texture).
+ *   Ids.  prim is the primitive's index in reference pre-order (hrt_debug_prim_record order 0), for sphere scenes and
+ *   general scenes alike; material is the material's id.  A scatter inside a ConstantMedium sets HRT_HIT_MEDIUM:
+ *   prim is then the medium's index (creation order of the flattened scene), normal (0, 0, 0), u = v = 0 and front clear, as a
+ *   render's record has it.
+ *   Medium draws.  A ConstantMedium draws its scatter distance from the sub-stream keyed by (params.seed, ray.pixel,
+ *   ray.sample, ray.segment, medium id), exactly a render's key for segment number `segment` of sample `sample` (the
+ *   ABSOLUTE sample index) of pixel `pixel` (y * width + x): a query with a path's key repeats that segment's draw.
+ *   HRT_QUERY_SKIP_MEDIA makes every medium transparent.
+ *   Miss.  flags = 0, t = the ray's t_max, prim = material = 0xFFFFFFFF, every other field +0.
+ *   Invalid ray.  A ray with a non-finite value in origin, direction, time or t_min, with a NaN t_max, with the
+ *   direction (0, 0, 0), for which t_min < t_max does not hold, or whose time lies outside [time0, time1], is not
+ *   traced: flags = HRT_HIT_INVALID, prim = material = 0xFFFFFFFF, every other field +0.
+ *   What a result depends on.  Hit i is a function of ray i, the params and the committed scene ALONE: never of n, of
+ *   the ray's position in the batch, of the other rays, of HRT_QUERY_NO_LDS or of the device.  d_hits[n ..] is never
+ *   written.  The call writes nothing in the scene and is re-entrant as the renders are; the work is asynchronous on
+ *   `stream`.
+ * d_rays and d_hits are device memory, n records of 48 bytes each, 16-byte aligned, and must not overlap.
+ * Errors, each changing nothing and answered before any device call: HRT_ERR_INVALID_ARG for a null scene, params or
+ * buffer (n == 0 is HRT_OK whatever the buffers, and launches nothing), a misaligned buffer, unknown flags,
+ * reserved != 0, time0 <= time1 not holding or a non-finite bound, n >= 2^32; HRT_ERR_STATE for an uncommitted scene. */
+typedef struct hrt_ray hrt_ray;
+struct hrt_ray { /* 48 bytes */
+  float origin[3];
+  float t_min;
+  float direction[3]; /* need not be normalised */
+  float t_max;        /* +inf allowed */
+  float time;
+  uint32_t pixel, sample, segment; /* the key of a ConstantMedium's draw (above); 0, 0, 0 is fine */
+};
+typedef struct hrt_hit hrt_hit;
+struct hrt_hit { /* 48 bytes: the reference's HitRecord (hit_record.rs) and the ids */
+  float t;
+  uint32_t prim;
+  uint32_t material;
+  uint32_t flags; /* HRT_HIT_* */
+  float point[3];
+  float u;
+  float normal[3];
+  float v;
+};
+enum { HRT_HIT_HIT = 1, HRT_HIT_FRONT = 2, HRT_HIT_MEDIUM = 4, HRT_HIT_INVALID = 8 };
+enum {
+  HRT_QUERY_SKIP_MEDIA = 1,    /* ConstantMedium nodes are transparent */
+  HRT_QUERY_NO_LDS = 2,        /* keep the scene in global memory even when it fits in LDS (A/B; the same hits) */
+  HRT_QUERY_REFERENCE_CULL = 4 /* aabb.rs's box test alone (the same hits) */
+};
+typedef struct hrt_query_params hrt_query_params;
+struct hrt_query_params { /* 24 bytes */
+  uint32_t flags;    /* HRT_QUERY_* bits */
+  uint32_t reserved; /* 0 */
+  float time0, time1; /* the interval the rays' times lie in: time0 <= time1, both finite */
+  uint64_t seed;      /* with (pixel, sample, segment) of a ray: the key of a medium's draw */
+};
+hrt_status hrt_scene_intersect(hrt_scene* s, const hrt_query_params* q, const hrt_ray* d_rays, uint64_t n, hrt_hit* d_hits,
+                               void* stream);
+/* ... with rays and hits in HOST memory: copies in, runs the device path on the scene's device, copies out; synchronous */
+hrt_status hrt_scene_intersect_host(hrt_scene* s, const hrt_query_params* q, const hrt_ray* rays, uint64_t n, hrt_hit* hits);
+/* The camera rays a render starts with: for every pixel of `tiles` (packed as hrt_render_tiles_device packs them) and
+ * k in [0, p->samples), ray (packed pixel index) * p->samples + k is the ray a radiance sample p->sample_offset + k of
+ * that pixel draws (lane.h start_sample: jitter, lens point, shutter time, from (p->seed, pixel, sample)), with
+ * t_min = p->t_min, t_max = +inf and key (y * width + x, p->sample_offset + k, 0).  So hrt_camera_rays followed by
+ * hrt_scene_intersect with p->seed and the camera's shutter as [time0, time1] gives the feature pass's first hits,
+ * sample by sample: hit, normal, and depth = t * sqrtf(dot(d, d)).  d_rays: device memory, (the tiles' pixels) x
+ * p->samples records, 16-byte aligned.  The checks are the render calls' (width, height, samples, known flags, the
+ * shutter, tiles inside the image); p->flags select nothing here.  More than 2^32 - 1 rays: HRT_ERR_INVALID_ARG.  A
+ * call with more than one tile reads its tile table from host memory and waits for `stream` before it returns. */
+hrt_status hrt_camera_rays(hrt_scene* s, const hrt_camera* cam, const hrt_render_params* p, const hrt_tile* tiles,
+                           uint32_t n_tiles, hrt_ray* d_rays, void* stream);
+/* ... into HOST memory; synchronous */
+hrt_status hrt_camera_rays_host(hrt_scene* s, const hrt_camera* cam, const hrt_render_params* p, const hrt_tile* tiles,
+                                uint32_t n_tiles, hrt_ray* rays);
+
 /* ---- diagnostics ---- */
 /* Device occupancy / layout facts of the committed scene (for DESIGN/bench). */
 typedef struct hrt_scene_info {
