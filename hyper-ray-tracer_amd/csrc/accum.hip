@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <memory>
 #include <type_traits>
 #include <vector>
 
@@ -265,38 +266,41 @@ struct hrt_accum {
   uint32_t width = 0, height = 0;
   std::vector<hrt_tile> tiles;
   size_t n_px = 0;
-  float4* d_acc = nullptr; /* n_px raw sums (x, y, z; w = 0), packed as the tiles are */
+  /* The host copies of d_ntiles, d_ftiles and d_mtiles, which stream-ordered copies read.  Every device buffer below is an
+   * owning DevBuf, freed with the accumulator (hrt_accum_destroy); these are declared before them all, so they go after
+   * them, when the frees have waited for the device. */
+  std::vector<NoiseTile> h_ntiles;
+  std::vector<filter::FilterTile> h_ftiles;
+  std::vector<MergeTile> h_mtiles;
+  DevBuf<float4> d_acc; /* n_px raw sums (x, y, z; w = 0), packed as the tiles are */
   bool has_identity = false;
   FrameIdentity identity;
   AccumLedger ledger; /* the samples and chunks (K) every tile holds */
   bool invalid = false; /* a pass was stopped by the walk watchdog: the sums are incomplete until a reset */
-  float* d_m2 = nullptr;   /* HRT_ACCUM_NOISE: n_px moments (accum.h), packed as d_acc */
+  DevBuf<float> d_m2; /* HRT_ACCUM_NOISE: n_px moments (accum.h), packed as d_acc */
   std::vector<uint32_t> tile_off; /* first pixel of each tile in the packed order */
-  NoiseTile* d_ntiles = nullptr; /* n_tiles records for accum_noise / accum_resolve_tiles, and their host copy */
-  float2* d_nout = nullptr;      /* n_tiles x (mean, max) */
-  std::vector<NoiseTile> h_ntiles;
+  DevBuf<NoiseTile> d_ntiles; /* n_tiles records for accum_noise / accum_resolve_tiles (host copy: h_ntiles) */
+  DevBuf<float2> d_nout; /* n_tiles x (mean, max) */
   /* The filtered resolve's buffers (filter.h), made by the first hrt_accum_resolve_filtered: two raster planes over
    * the tiles' bounding box and the tiles in plane coordinates.  f_state: 0 not made yet, 1 made, -1 the tiles overlap */
   int f_state = 0;
   uint32_t f_w = 0, f_h = 0, f_blocks = 0;
-  float4* d_fplane[2] = {nullptr, nullptr};
-  filter::FilterTile* d_ftiles = nullptr;
-  std::vector<filter::FilterTile> h_ftiles;
+  DevBuf<float4> d_fplane[2];
+  DevBuf<filter::FilterTile> d_ftiles;
   /* HRT_ACCUM_FEATURES: the two planes of first-hit feature sums (feature_pass.h: fa = (albedo.xyz, hit), fn = (normal.xyz,
    * depth)), packed as d_acc, the feature samples held (a ledger of its own: every feature pass covers every tile) and
    * the tiles as feature_kernel sees them */
-  float4 *d_fa = nullptr, *d_fn = nullptr;
+  DevBuf<float4> d_fa, d_fn;
   AccumLedger f_ledger;
-  features::FeatureTile* d_feat_tiles = nullptr;
+  DevBuf<features::FeatureTile> d_feat_tiles;
   uint32_t feat_blocks = 0, feat_log_bw = 0;
   /* the guided resolve's two mean feature rasters over the planes' bounding box, made by the first guided resolve */
-  float4* d_gplane[2] = {nullptr, nullptr};
+  DevBuf<float4> d_gplane[2];
   /* hrt_accum_noise_filtered's packed per-pixel errs when the caller keeps none (n_px f32), made by the first such call;
    * scratch like the rasters: not part of a snapshot */
-  float* d_ferr = nullptr;
-  /* hrt_accum_merge_tiles' table of the selected tiles, made by the first such merge, and its host copy */
-  MergeTile* d_mtiles = nullptr;
-  std::vector<MergeTile> h_mtiles;
+  DevBuf<float> d_ferr;
+  /* hrt_accum_merge_tiles' table of the selected tiles, made by the first such merge (host copy: h_mtiles) */
+  DevBuf<MergeTile> d_mtiles;
 };
 
 namespace {
@@ -306,6 +310,10 @@ void accum_usable(const hrt_accum* a) {
 }
 void accum_format(int32_t format) {
   if (format != HRT_ACCUM_F32 && format != HRT_ACCUM_RGBA8) throw HipError{HRT_ERR_INVALID_ARG, "unknown HRT_ACCUM_* format"};
+}
+/* the floor of a noise estimate's denominator */
+void noise_floor(float floor, const char* who) {
+  if (!(floor > 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, std::string(who) + ": floor must be > 0"};
 }
 void check_identity(const hrt_accum* a, const FrameIdentity& id) {
   if (id.width != a->width || id.height != a->height)
@@ -322,6 +330,12 @@ void accum_uniform(const hrt_accum* a, hrt_status st, const char* what) {
 }
 void accum_holds_samples(const hrt_accum* a) {
   if (a->ledger.empty()) throw HipError{HRT_ERR_STATE, "the accumulator holds no samples"};
+}
+/* the samples a pass adds, and the identity the accumulator takes from the pass (or merge, or upload) that went in */
+SampleRange pass_range(const hrt_render_params* p) { return SampleRange{p->sample_offset, (uint64_t)p->sample_offset + p->samples}; }
+void adopt_identity(hrt_accum* a, const FrameIdentity& id) {
+  a->identity = id;
+  a->has_identity = true;
 }
 /* the record of n pixels from `off` on that hold `samples` samples in `chunks` chunks */
 NoiseTile noise_tile(uint32_t off, uint32_t n, uint64_t samples, uint64_t chunks) {
@@ -341,8 +355,21 @@ void upload_noise_tiles(hrt_accum* a, hipStream_t stream) {
   a->h_ntiles.resize(nt);
   for (size_t t = 0; t < nt; t++)
     a->h_ntiles[t] = noise_tile(a->tile_off[t], a->tiles[t].w * a->tiles[t].h, a->ledger.samples(t), a->ledger.chunks(t));
-  hip_check(hipMemcpyAsync(a->d_ntiles, a->h_ntiles.data(), nt * sizeof(NoiseTile), hipMemcpyHostToDevice, stream),
+  hip_check(hipMemcpyAsync(a->d_ntiles.p, a->h_ntiles.data(), nt * sizeof(NoiseTile), hipMemcpyHostToDevice, stream),
             "hipMemcpyAsync(noise tiles)");
+}
+/* the (mean, max) a reduction left in d_nout, waited for, with what the ledger says each tile holds */
+void read_tile_noise(hrt_accum* a, hipStream_t stream, hrt_tile_noise* tiles_out) {
+  const size_t nt = a->tiles.size();
+  std::vector<float2> rec(nt);
+  hip_check(hipMemcpyAsync(rec.data(), a->d_nout.p, nt * sizeof(float2), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(noise records)");
+  hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize(noise)");
+  for (size_t t = 0; t < nt; t++) {
+    tiles_out[t].mean = rec[t].x;
+    tiles_out[t].max = rec[t].y;
+    tiles_out[t].samples = a->ledger.samples(t);
+    tiles_out[t].chunks = a->ledger.chunks(t);
+  }
 }
 /* tiles that hold different sample counts resolve each with its own (accum_resolve_tiles); every tile needs samples */
 void launch_resolve_tiles(hrt_accum* a, int32_t format, void* d_out, hipStream_t stream) {
@@ -351,35 +378,105 @@ void launch_resolve_tiles(hrt_accum* a, int32_t format, void* d_out, hipStream_t
     if (a->ledger.samples(t) == 0) throw HipError{HRT_ERR_STATE, "a tile of the accumulator holds no samples"};
   upload_noise_tiles(a, stream);
   with_format(format, [&](auto fc) {
-    hipLaunchKernelGGL((accum_resolve_tiles<decltype(fc)::value>), dim3(blocks), dim3(256), 0, stream, (const float4*)a->d_acc,
-                       (const NoiseTile*)a->d_ntiles, nt, d_out);
+    hipLaunchKernelGGL((accum_resolve_tiles<decltype(fc)::value>), dim3(blocks), dim3(256), 0, stream, (const float4*)a->d_acc.p,
+                       (const NoiseTile*)a->d_ntiles.p, nt, d_out);
   });
   hip_check(hipGetLastError(), "accum_resolve_tiles launch");
 }
 void launch_resolve(hrt_accum* a, int32_t format, void* d_out, hipStream_t stream) {
   if (!a->ledger.uniform()) return launch_resolve_tiles(a, format, d_out, stream);
-  resolve_pixels(format, a->d_acc, a->n_px, accum::resolve_scale(a->ledger.samples(0)), d_out, stream);
+  resolve_pixels(format, a->d_acc.p, a->n_px, accum::resolve_scale(a->ledger.samples(0)), d_out, stream);
 }
 
+/* ---- the filtered calls.  One description of a call, whichever public struct it came in: the variance-guided filter
+ * (hrt_filter_params), with the feature terms (hrt_guided_params), with the demodulation option (hrt_guided_ex_params) */
 constexpr filter::Demod NO_DEMOD{false, 0.0f};
+struct FilterCall {
+  uint32_t iterations;
+  float sigma;
+  filter::Terms K;
+  filter::Demod demod;
+  bool guided;            /* reads the feature planes; false: the variance-only filter, which asks for none */
+  float err_floor = 0.0f; /* of the filtered noise estimate (filter::FORMAT_ERR), not read otherwise */
+};
 
-/* hrt_accum_resolve_filtered's checks: nothing changes on an error */
-void filter_args(const hrt_filter_params* f) {
-  if (f->iterations < 1 || f->iterations > filter::MAX_ITERATIONS)
-    throw HipError{HRT_ERR_INVALID_ARG, "hrt_filter_params: iterations outside [1, 5]"};
-  if (!(f->sigma > 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_filter_params: sigma must be > 0"};
+/* the argument checks, in the order the refusals are documented in: iterations and sigma, the tolerances, reserved, the
+ * flags and the floor.  Nothing changes on an error */
+void filter_args(uint32_t iterations, float sigma) {
+  if (iterations < 1 || iterations > filter::MAX_ITERATIONS) throw HipError{HRT_ERR_INVALID_ARG, "filter: iterations outside [1, 5]"};
+  if (!(sigma > 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "filter: sigma must be > 0"};
 }
-void filter_state(const hrt_accum* a) {
+/* a tolerance as filter.h takes it */
+float guided_term(float tolerance) {
+  if (!(tolerance >= 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "guided filter: a tolerance is negative or NaN"};
+  return tolerance > 0.0f ? 1.0f / tolerance : 0.0f;
+}
+/* the HRT_GUIDED_* flags and, with HRT_GUIDED_DEMODULATE, the floor (not read otherwise) */
+filter::Demod guided_ex_option(uint32_t flags, float albedo_floor) {
+  if (flags & ~(uint32_t)HRT_GUIDED_DEMODULATE) throw HipError{HRT_ERR_INVALID_ARG, "guided filter: unknown HRT_GUIDED_* flag bits"};
+  if (!(flags & HRT_GUIDED_DEMODULATE)) return NO_DEMOD;
+  if (!(albedo_floor > 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "guided filter: albedo_floor must be > 0 with HRT_GUIDED_DEMODULATE"};
+  return filter::Demod{true, albedo_floor};
+}
+FilterCall filter_call(const hrt_filter_params* f) {
+  filter_args(f->iterations, f->sigma);
+  return FilterCall{f->iterations, f->sigma, filter::Terms{}, NO_DEMOD, false};
+}
+FilterCall filter_call(const hrt_guided_params* g) {
+  filter_args(g->iterations, g->sigma);
+  return FilterCall{g->iterations, g->sigma, filter::Terms{guided_term(g->normal), guided_term(g->albedo), guided_term(g->depth)}, NO_DEMOD, true};
+}
+FilterCall filter_call(const hrt_guided_ex_params* g) {
+  filter_args(g->iterations, g->sigma);
+  const filter::Terms K{guided_term(g->normal), guided_term(g->albedo), guided_term(g->depth)};
+  if (g->reserved != 0) throw HipError{HRT_ERR_INVALID_ARG, "hrt_guided_ex_params: reserved must be 0"};
+  return FilterCall{g->iterations, g->sigma, K, guided_ex_option(g->flags, g->albedo_floor), true};
+}
+/* no term and no flag: the variance-only filter (the noise estimates take it without feature planes; a guided resolve
+ * stays guided) */
+bool variance_only(const filter::Terms& K, const filter::Demod& demod) { return !demod.on && K.kn == 0.0f && K.ka == 0.0f && K.kz == 0.0f; }
+
+uint64_t feature_samples(const hrt_accum* a) { return a->f_ledger.samples(0); }
+void features_flag(const hrt_accum* a, const char* who) {
+  if (!a->d_fa.p) throw HipError{HRT_ERR_STATE, std::string(who) + ": the accumulator was created without HRT_ACCUM_FEATURES"};
+}
+/* what the accumulator must hold for the call, in the documented order: usable, the feature planes (guided), the noise
+ * plane, samples, two chunks in every tile, feature samples (guided) */
+void filtered_state(const hrt_accum* a, const FilterCall& c, const char* who) {
+  const auto refuse = [who](const char* why) { throw HipError{HRT_ERR_STATE, std::string(who) + why}; }; /* no string on the way through */
   accum_usable(a);
-  if (!a->d_m2) throw HipError{HRT_ERR_STATE, "hrt_accum_resolve_filtered: the accumulator was created without HRT_ACCUM_NOISE"};
+  if (c.guided) features_flag(a, who);
+  if (!a->d_m2.p) refuse(": the accumulator was created without HRT_ACCUM_NOISE");
   accum_holds_samples(a);
   for (size_t t = 0; t < a->tiles.size(); t++)
-    if (a->ledger.samples(t) == 0 || a->ledger.chunks(t) < 2)
-      throw HipError{HRT_ERR_STATE, "hrt_accum_resolve_filtered: a tile holds no samples or fewer than 2 chunks (no variance estimate)"};
+    if (a->ledger.samples(t) == 0 || a->ledger.chunks(t) < 2) refuse(": a tile holds no samples or fewer than 2 chunks (no variance estimate)");
+  if (c.guided && feature_samples(a) == 0) refuse(": the accumulator holds no feature samples");
 }
-/* the planes and the tile records, once per accumulator: its tiles never change */
+
+/* whether the tiles, relative to (x0, y0), lie inside a w x h raster and cover no pixel twice and none that `absent`
+ * (of the pixel's raster index) names */
+enum class TileCover { OK, OUTSIDE, OVERLAP };
+template <class Absent>
+TileCover tile_cover(const hrt_tile* tiles, size_t n_tiles, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, Absent&& absent) {
+  std::vector<bool> covered((size_t)w * h, false);
+  for (size_t t = 0; t < n_tiles; t++) {
+    const hrt_tile& T = tiles[t];
+    if (T.w == 0 || T.h == 0 || T.x < x0 || T.y < y0 || T.x - x0 >= w || T.y - y0 >= h || T.w > w - (T.x - x0) || T.h > h - (T.y - y0))
+      return TileCover::OUTSIDE;
+    for (uint32_t y = T.y - y0; y < T.y - y0 + T.h; y++)
+      for (uint32_t x = T.x - x0; x < T.x - x0 + T.w; x++) {
+        const size_t k = (size_t)y * w + x;
+        if (covered[k] || absent(k)) return TileCover::OVERLAP;
+        covered[k] = true;
+      }
+  }
+  return TileCover::OK;
+}
+
+/* the planes and the tile records, once per accumulator: its tiles never change.  Built into locals and moved in at the
+ * end: a failure half-way leaves nothing made and f_state 0 */
 void filter_prepare(hrt_accum* a, hipStream_t stream) {
-  if (a->f_state < 0) throw HipError{HRT_ERR_UNSUPPORTED, "hrt_accum_resolve_filtered: the accumulator's tiles overlap"};
+  if (a->f_state < 0) throw HipError{HRT_ERR_UNSUPPORTED, "filtered resolve: the accumulator's tiles overlap"};
   if (a->f_state > 0) return;
   uint32_t x0 = UINT32_MAX, y0 = UINT32_MAX, x1 = 0, y1 = 0;
   for (const hrt_tile& t : a->tiles) {
@@ -388,17 +485,10 @@ void filter_prepare(hrt_accum* a, hipStream_t stream) {
   }
   const uint32_t w = x1 - x0, h = y1 - y0;
   const size_t area = (size_t)w * h;
-  /* disjoint tiles cover as many pixels as they hold */
-  std::vector<bool> covered(area, false);
-  for (const hrt_tile& t : a->tiles)
-    for (uint32_t y = t.y - y0; y < t.y - y0 + t.h; y++)
-      for (uint32_t x = t.x - x0; x < t.x - x0 + t.w; x++) {
-        if (covered[(size_t)y * w + x]) {
-          a->f_state = -1;
-          throw HipError{HRT_ERR_UNSUPPORTED, "hrt_accum_resolve_filtered: the accumulator's tiles overlap"};
-        }
-        covered[(size_t)y * w + x] = true;
-      }
+  if (tile_cover(a->tiles.data(), a->tiles.size(), x0, y0, w, h, [](size_t) { return false; }) != TileCover::OK) {
+    a->f_state = -1;
+    throw HipError{HRT_ERR_UNSUPPORTED, "filtered resolve: the accumulator's tiles overlap"};
+  }
   std::vector<filter::FilterTile> ft(a->tiles.size());
   uint64_t blocks = 0;
   for (size_t t = 0; t < ft.size(); t++) {
@@ -406,32 +496,24 @@ void filter_prepare(hrt_accum* a, hipStream_t stream) {
     ft[t] = filter::FilterTile{T.x - x0, T.y - y0, T.w, T.h, a->tile_off[t], (uint32_t)blocks, 0.0f, 0.0f};
     blocks += filter::tile_blocks(T.w, T.h);
   }
-  if (blocks >= (1ull << 31)) throw HipError{HRT_ERR_UNSUPPORTED, "hrt_accum_resolve_filtered: too many tile blocks for one launch"};
-  float4* plane[2] = {nullptr, nullptr};
-  filter::FilterTile* d_ft = nullptr;
-  try {
-    for (float4*& pl : plane) hip_check(hipMalloc((void**)&pl, area * sizeof(float4)), "hipMalloc(filter plane)");
-    hip_check(hipMalloc((void**)&d_ft, ft.size() * sizeof(filter::FilterTile)), "hipMalloc(filter tiles)");
-    /* pixels no tile covers are absent: v < 0 (0xBFBFBFBF is -1.498).  filter_gather writes the covered ones of
-     * plane 0 alone and every iteration passes absent pixels on, so once is enough; it is waited for, so that a
-     * later resolve on another stream finds it done */
-    if (a->n_px != area) {
-      hip_check(hipMemsetAsync(plane[0], 0xBF, area * sizeof(float4), stream), "hipMemsetAsync(filter plane)");
-      hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize(filter plane)");
-    }
-  } catch (...) {
-    for (float4* pl : plane)
-      if (pl) (void)hipFree(pl);
-    if (d_ft) (void)hipFree(d_ft);
-    throw;
+  if (blocks >= (1ull << 31)) throw HipError{HRT_ERR_UNSUPPORTED, "filtered resolve: too many tile blocks for one launch"};
+  DevBuf<float4> plane[2];
+  DevBuf<filter::FilterTile> d_ft;
+  for (DevBuf<float4>& pl : plane) pl.alloc(area * sizeof(float4), "hipMalloc(filter plane)");
+  d_ft.alloc(ft.size() * sizeof(filter::FilterTile), "hipMalloc(filter tiles)");
+  /* pixels no tile covers are absent: v < 0 (0xBFBFBFBF is -1.498).  filter_gather writes the covered ones of
+   * plane 0 alone and every iteration passes absent pixels on, so once is enough; it is waited for, so that a
+   * later resolve on another stream finds it done */
+  if (a->n_px != area) {
+    hip_check(hipMemsetAsync(plane[0].p, 0xBF, area * sizeof(float4), stream), "hipMemsetAsync(filter plane)");
+    hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize(filter plane)");
   }
-  a->d_fplane[0] = plane[0], a->d_fplane[1] = plane[1];
-  a->d_ftiles = d_ft;
+  for (int k = 0; k < 2; k++) a->d_fplane[k] = std::move(plane[k]);
+  a->d_ftiles = std::move(d_ft);
   a->h_ftiles.swap(ft);
   a->f_w = w, a->f_h = h, a->f_blocks = (uint32_t)blocks;
   a->f_state = 1;
 }
-uint64_t feature_samples(const hrt_accum* a) { return a->f_ledger.samples(0); }
 /* the sums and m2 gathered onto plane 0; demod.on: demodulated by the mean albedo in the same pass */
 void filter_gather_plane(hrt_accum* a, const filter::Demod& demod, hipStream_t stream) {
   filter_prepare(a, stream);
@@ -441,72 +523,33 @@ void filter_gather_plane(hrt_accum* a, const filter::Demod& demod, hipStream_t s
     a->h_ftiles[t].inv_n = a->h_ntiles[t].inv_n;
     a->h_ftiles[t].inv_k1 = a->h_ntiles[t].inv_k1;
   }
-  hip_check(hipMemcpyAsync(a->d_ftiles, a->h_ftiles.data(), nt * sizeof(filter::FilterTile), hipMemcpyHostToDevice, stream),
+  hip_check(hipMemcpyAsync(a->d_ftiles.p, a->h_ftiles.data(), nt * sizeof(filter::FilterTile), hipMemcpyHostToDevice, stream),
             "hipMemcpyAsync(filter tiles)");
   if (demod.on)
-    filter::launch_gather_demod(a->d_acc, a->d_m2, a->d_fa, 1.0f / (float)feature_samples(a), demod.floor, a->d_ftiles, nt, a->f_blocks,
-                                a->d_fplane[0], a->f_w, stream);
+    filter::launch_gather_demod(a->d_acc.p, a->d_m2.p, a->d_fa.p, 1.0f / (float)feature_samples(a), demod.floor, a->d_ftiles.p, nt, a->f_blocks,
+                                a->d_fplane[0].p, a->f_w, stream);
   else
-    filter::launch_gather(a->d_acc, a->d_m2, a->d_ftiles, nt, a->f_blocks, a->d_fplane[0], a->f_w, stream);
+    filter::launch_gather(a->d_acc.p, a->d_m2.p, a->d_ftiles.p, nt, a->f_blocks, a->d_fplane[0].p, a->f_w, stream);
 }
-/* the filtered resolve, or with the terms K the guided one: the colour plane gathered, the feature rasters if guided,
- * then the iterations.  demod (a guided resolve's option, filter.h): the plane is gathered demodulated and the last
- * iteration remodulates.  format filter::FORMAT_ERR: d_out takes the filtered noise estimate against err_floor */
-void launch_filtered(hrt_accum* a, uint32_t iterations, float sigma, const filter::Terms* K, const filter::Demod& demod, int32_t format,
-                     void* d_out, hipStream_t stream, float err_floor = 0.0f) {
-  filter_gather_plane(a, K ? demod : NO_DEMOD, stream);
+/* A filtered call after its checks: the colour plane gathered, the feature rasters if the call is guided, then the
+ * iterations.  c.demod.on: the plane is gathered demodulated and the last iteration remodulates.  format
+ * filter::FORMAT_ERR: d_out takes the filtered noise estimate against c.err_floor.  (A call that is not guided carries
+ * no term and no option: filter_call, variance_only.) */
+void launch_filtered(hrt_accum* a, const FilterCall& c, int32_t format, void* d_out, hipStream_t stream) {
+  filter_gather_plane(a, c.demod, stream);
   const uint32_t nt = (uint32_t)a->tiles.size();
-  if (K && !a->d_gplane[0]) { /* the two feature rasters, once: a present pixel's features are written by every resolve */
-    float4* plane[2] = {nullptr, nullptr};
-    try {
-      for (float4*& pl : plane) hip_check(hipMalloc((void**)&pl, (size_t)a->f_w * a->f_h * sizeof(float4)), "hipMalloc(feature raster)");
-    } catch (...) {
-      if (plane[0]) (void)hipFree(plane[0]);
-      throw;
-    }
-    a->d_gplane[0] = plane[0], a->d_gplane[1] = plane[1];
-  }
-  float4 *albedo = K ? a->d_gplane[0] : nullptr, *normal = K ? a->d_gplane[1] : nullptr;
-  if (K)
-    filter::launch_gather_features(a->d_fa, a->d_fn, a->d_ftiles, nt, a->f_blocks, 1.0f / (float)feature_samples(a), albedo, normal,
+  float4 *albedo = nullptr, *normal = nullptr;
+  if (c.guided) {
+    /* the two feature rasters, once: a present pixel's features are written by every resolve ([1] is made last, so a
+     * failure between the two makes both again) */
+    if (!a->d_gplane[1].p)
+      for (DevBuf<float4>& pl : a->d_gplane) pl.alloc((size_t)a->f_w * a->f_h * sizeof(float4), "hipMalloc(feature raster)");
+    albedo = a->d_gplane[0].p, normal = a->d_gplane[1].p;
+    filter::launch_gather_features(a->d_fa.p, a->d_fn.p, a->d_ftiles.p, nt, a->f_blocks, 1.0f / (float)feature_samples(a), albedo, normal,
                                    a->f_w, stream);
-  filter::launch_atrous(a->d_fplane[0], a->d_fplane[1], albedo, normal, a->f_w, a->f_h, a->d_ftiles, nt, a->f_blocks, iterations, sigma,
-                        K ? *K : filter::Terms{}, K ? demod : NO_DEMOD, format, d_out, stream, err_floor);
-}
-
-/* hrt_accum_resolve_guided's checks beyond the filtered resolve's, and its tolerances as filter.h takes them */
-float guided_term(float tolerance) {
-  if (!(tolerance >= 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_guided_params: a tolerance is negative or NaN"};
-  return tolerance > 0.0f ? 1.0f / tolerance : 0.0f;
-}
-filter::Terms guided_args(const hrt_guided_params* g) {
-  const hrt_filter_params f{g->iterations, g->sigma};
-  filter_args(&f);
-  return filter::Terms{guided_term(g->normal), guided_term(g->albedo), guided_term(g->depth)};
-}
-/* hrt_guided_ex_params' checks beyond guided_args': its flags, reserved and, with HRT_GUIDED_DEMODULATE, the floor (not
- * read otherwise) */
-filter::Demod guided_ex_option(uint32_t flags, float albedo_floor) {
-  if (flags & ~(uint32_t)HRT_GUIDED_DEMODULATE) throw HipError{HRT_ERR_INVALID_ARG, "hrt_guided_ex_params: unknown HRT_GUIDED_* flag bits"};
-  if (!(flags & HRT_GUIDED_DEMODULATE)) return NO_DEMOD;
-  if (!(albedo_floor > 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_guided_ex_params: albedo_floor must be > 0 with HRT_GUIDED_DEMODULATE"};
-  return filter::Demod{true, albedo_floor};
-}
-filter::Terms guided_ex_args(const hrt_guided_ex_params* g, filter::Demod& demod) {
-  const hrt_guided_params base{g->iterations, g->sigma, g->normal, g->albedo, g->depth};
-  const filter::Terms K = guided_args(&base);
-  if (g->reserved != 0) throw HipError{HRT_ERR_INVALID_ARG, "hrt_guided_ex_params: reserved must be 0"};
-  demod = guided_ex_option(g->flags, g->albedo_floor);
-  return K;
-}
-void features_flag(const hrt_accum* a, const char* who) {
-  if (!a->d_fa) throw HipError{HRT_ERR_STATE, std::string(who) + ": the accumulator was created without HRT_ACCUM_FEATURES"};
-}
-void guided_state(const hrt_accum* a) {
-  accum_usable(a);
-  features_flag(a, "hrt_accum_resolve_guided");
-  filter_state(a);
-  if (feature_samples(a) == 0) throw HipError{HRT_ERR_STATE, "hrt_accum_resolve_guided: the accumulator holds no feature samples"};
+  }
+  filter::launch_atrous(a->d_fplane[0].p, a->d_fplane[1].p, albedo, normal, a->f_w, a->f_h, a->d_ftiles.p, nt, a->f_blocks, c.iterations,
+                        c.sigma, c.K, c.demod, format, d_out, stream, c.err_floor);
 }
 
 /* hrt_accum_resolve_host / _filtered_host after their checks: `launch` resolves into a buffer of the scene's pool on
@@ -549,14 +592,14 @@ void accum_add(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, 
   }
   const FrameIdentity id = frame_identity(cam, p);
   check_identity(a, id);
-  const SampleRange r{p->sample_offset, (uint64_t)p->sample_offset + p->samples};
+  const SampleRange r = pass_range(p);
   if (p->samples != 0) check_range(a->ledger.may_add(r, idx, n)); /* samples = 0: check_render_args reports it */
   SumsDest dst;
-  dst.d_acc = a->d_acc;
-  dst.d_m2 = a->d_m2;
+  dst.d_acc = a->d_acc.p;
+  dst.d_m2 = a->d_m2.p;
   /* a subset always takes the mapped kernel (launched tile i is the accumulator's tile idx[i]); the whole frame only
    * with a noise plane: without, the plain kernel, as ever (the tiles map onto themselves) */
-  dst.mapped = idx || a->d_m2;
+  dst.mapped = idx || a->d_m2.p;
   dst.acc_offs = idx ? offs.data() : nullptr;
   if (d_out) { /* the whole frame of a uniform accumulator: every tile holds samples(0) */
     dst.preview = format;
@@ -570,25 +613,28 @@ void accum_add(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, 
     if (launched) a->invalid = true; /* the pass is (partly) in the sums and cannot be taken out again */
     throw;
   }
-  a->identity = id;
-  a->has_identity = true;
+  adopt_identity(a, id);
   a->ledger.record(r, pass_chunks(a->scene, p), idx, n);
 }
 
-/* hrt_accum_merge's preconditions beyond usable: the same device, image, tiles and planes on both sides */
-void merge_compatible(const hrt_accum* dst, const hrt_accum* src, const char* who) {
-  const std::string w(who);
-  if ((dst->d_m2 != nullptr) != (src->d_m2 != nullptr))
-    throw HipError{HRT_ERR_INVALID_ARG, w + ": one accumulator keeps a noise plane (HRT_ACCUM_NOISE), the other none"};
+/* A merge's preconditions beyond usable, in the order they are refused in: the same noise plane or none, uniform on
+ * both sides (hrt_accum_merge alone: hrt_accum_merge_tiles is the merge for tiles that hold different passes), the
+ * same device, image and tiles, the same feature planes or none */
+void merge_compatible(const hrt_accum* dst, const hrt_accum* src, const char* who, bool uniform) {
+  const auto refuse = [who](hrt_status st, const char* why) { throw HipError{st, std::string(who) + why}; };
+  if ((dst->d_m2.p != nullptr) != (src->d_m2.p != nullptr))
+    refuse(HRT_ERR_INVALID_ARG, ": one accumulator keeps a noise plane (HRT_ACCUM_NOISE), the other none");
+  if (uniform && !(dst->ledger.uniform() && src->ledger.uniform()))
+    refuse(HRT_ERR_UNSUPPORTED, ": the accumulator's tiles hold different passes");
   if (dst->device != src->device || dst->width != src->width || dst->height != src->height || dst->tiles.size() != src->tiles.size() ||
       memcmp(dst->tiles.data(), src->tiles.data(), dst->tiles.size() * sizeof(hrt_tile)) != 0)
-    throw HipError{HRT_ERR_INVALID_ARG, w + ": the accumulators differ in device, image size or tiles"};
-  if ((dst->d_fa != nullptr) != (src->d_fa != nullptr))
-    throw HipError{HRT_ERR_INVALID_ARG, w + ": one accumulator keeps feature planes (HRT_ACCUM_FEATURES), the other none"};
+    refuse(HRT_ERR_INVALID_ARG, ": the accumulators differ in device, image size or tiles");
+  if ((dst->d_fa.p != nullptr) != (src->d_fa.p != nullptr))
+    refuse(HRT_ERR_INVALID_ARG, ": one accumulator keeps feature planes (HRT_ACCUM_FEATURES), the other none");
 }
 
 /* ---- snapshots (accum_snapshot.h is the codec; here: the accumulator's state into and out of its State) ---- */
-uint32_t accum_flags(const hrt_accum* a) { return (a->d_m2 ? HRT_ACCUM_NOISE : 0u) | (a->d_fa ? HRT_ACCUM_FEATURES : 0u); }
+uint32_t accum_flags(const hrt_accum* a) { return (a->d_m2.p ? HRT_ACCUM_NOISE : 0u) | (a->d_fa.p ? HRT_ACCUM_FEATURES : 0u); }
 /* the identity's 128 bytes as hrt.h lays them out; width and height are the accumulator's */
 void identity_bytes(const FrameIdentity& id, uint8_t* out) {
   static_assert(sizeof(hrt_camera) == 96, "the snapshot layout holds 96 camera bytes");
@@ -621,7 +667,7 @@ snapshot::State snapshot_state(const hrt_accum* a) {
   s.has_identity = a->has_identity;
   if (a->has_identity) identity_bytes(a->identity, s.identity);
   s.records = a->ledger.records();
-  if (a->d_fa) s.f_ranges = *a->f_ledger.ranges(); /* every feature pass covers every tile: always the shared record */
+  if (a->d_fa.p) s.f_ranges = *a->f_ledger.ranges(); /* every feature pass covers every tile: always the shared record */
   snapshot::layout(s);
   return s;
 }
@@ -657,7 +703,7 @@ hrt_status hrt_accum_create_ex(hrt_scene* s, uint32_t width, uint32_t height, co
     if (n_px >= (1ull << 32)) throw HipError{HRT_ERR_UNSUPPORTED, "more than 2^32 pixels in one accumulator"};
     if (!s->committed || !s->d_blob) throw HipError{HRT_ERR_STATE, "scene not committed"};
     DeviceGuard dg(s->device);
-    hrt_accum* a = new hrt_accum();
+    std::unique_ptr<hrt_accum> a(new hrt_accum()); /* a failure below frees what was made, on the device dg has set */
     a->scene = s;
     a->device = s->device;
     a->width = width;
@@ -670,39 +716,34 @@ hrt_status hrt_accum_create_ex(hrt_scene* s, uint32_t width, uint32_t height, co
       a->tile_off[i] = off;
       off += tiles[i].w * tiles[i].h;
     }
-    try {
-      hip_check(hipMalloc((void**)&a->d_acc, a->n_px * sizeof(float4)), "hipMalloc(accumulator)");
-      hip_check(hipMemset(a->d_acc, 0, a->n_px * sizeof(float4)), "hipMemset(accumulator)");
-      hip_check(hipMalloc((void**)&a->d_ntiles, n_tiles * sizeof(NoiseTile)), "hipMalloc(accumulator tiles)");
-      if (flags & HRT_ACCUM_NOISE) {
-        hip_check(hipMalloc((void**)&a->d_m2, a->n_px * sizeof(float)), "hipMalloc(noise plane)");
-        hip_check(hipMemset(a->d_m2, 0, a->n_px * sizeof(float)), "hipMemset(noise plane)");
-        hip_check(hipMalloc((void**)&a->d_nout, n_tiles * sizeof(float2)), "hipMalloc(noise records)");
-      }
-      if (flags & HRT_ACCUM_FEATURES) {
-        a->f_ledger = AccumLedger(n_tiles);
-        a->feat_log_bw = features::block_log_w();
-        std::vector<features::FeatureTile> ft(n_tiles);
-        uint64_t blocks = 0;
-        for (uint32_t i = 0; i < n_tiles; i++) {
-          ft[i] = features::FeatureTile{tiles[i].x, tiles[i].y, tiles[i].w, tiles[i].h, a->tile_off[i], (uint32_t)blocks, {0u, 0u}};
-          blocks += features::tile_blocks(tiles[i].w, tiles[i].h, a->feat_log_bw);
-        }
-        if (blocks >= (1ull << 31)) throw HipError{HRT_ERR_UNSUPPORTED, "HRT_ACCUM_FEATURES: too many tile blocks for one launch"};
-        a->feat_blocks = (uint32_t)blocks;
-        for (float4** pl : {&a->d_fa, &a->d_fn}) {
-          hip_check(hipMalloc((void**)pl, a->n_px * sizeof(float4)), "hipMalloc(feature plane)");
-          hip_check(hipMemset(*pl, 0, a->n_px * sizeof(float4)), "hipMemset(feature plane)");
-        }
-        hip_check(hipMalloc((void**)&a->d_feat_tiles, n_tiles * sizeof(features::FeatureTile)), "hipMalloc(feature tiles)");
-        hip_check(hipMemcpy(a->d_feat_tiles, ft.data(), n_tiles * sizeof(features::FeatureTile), hipMemcpyHostToDevice),
-                  "hipMemcpy(feature tiles)");
-      }
-    } catch (...) {
-      hrt_accum_destroy(a);
-      throw;
+    a->d_acc.alloc(a->n_px * sizeof(float4), "hipMalloc(accumulator)");
+    hip_check(hipMemset(a->d_acc.p, 0, a->n_px * sizeof(float4)), "hipMemset(accumulator)");
+    a->d_ntiles.alloc(n_tiles * sizeof(NoiseTile), "hipMalloc(accumulator tiles)");
+    if (flags & HRT_ACCUM_NOISE) {
+      a->d_m2.alloc(a->n_px * sizeof(float), "hipMalloc(noise plane)");
+      hip_check(hipMemset(a->d_m2.p, 0, a->n_px * sizeof(float)), "hipMemset(noise plane)");
+      a->d_nout.alloc(n_tiles * sizeof(float2), "hipMalloc(noise records)");
     }
-    *out = a;
+    if (flags & HRT_ACCUM_FEATURES) {
+      a->f_ledger = AccumLedger(n_tiles);
+      a->feat_log_bw = features::block_log_w();
+      std::vector<features::FeatureTile> ft(n_tiles);
+      uint64_t blocks = 0;
+      for (uint32_t i = 0; i < n_tiles; i++) {
+        ft[i] = features::FeatureTile{tiles[i].x, tiles[i].y, tiles[i].w, tiles[i].h, a->tile_off[i], (uint32_t)blocks, {0u, 0u}};
+        blocks += features::tile_blocks(tiles[i].w, tiles[i].h, a->feat_log_bw);
+      }
+      if (blocks >= (1ull << 31)) throw HipError{HRT_ERR_UNSUPPORTED, "HRT_ACCUM_FEATURES: too many tile blocks for one launch"};
+      a->feat_blocks = (uint32_t)blocks;
+      for (DevBuf<float4>* pl : {&a->d_fa, &a->d_fn}) {
+        pl->alloc(a->n_px * sizeof(float4), "hipMalloc(feature plane)");
+        hip_check(hipMemset(pl->p, 0, a->n_px * sizeof(float4)), "hipMemset(feature plane)");
+      }
+      a->d_feat_tiles.alloc(n_tiles * sizeof(features::FeatureTile), "hipMalloc(feature tiles)");
+      hip_check(hipMemcpy(a->d_feat_tiles.p, ft.data(), n_tiles * sizeof(features::FeatureTile), hipMemcpyHostToDevice),
+                "hipMemcpy(feature tiles)");
+    }
+    *out = a.release();
   });
 }
 
@@ -711,27 +752,17 @@ void hrt_accum_destroy(hrt_accum* a) {
   int prev = -1;
   (void)hipGetDevice(&prev);
   (void)hipSetDevice(a->device);
-  if (a->d_acc) (void)hipFree(a->d_acc); /* waits for the work that uses it */
-  if (a->d_m2) (void)hipFree(a->d_m2);
-  if (a->d_ntiles) (void)hipFree(a->d_ntiles);
-  if (a->d_nout) (void)hipFree(a->d_nout);
-  for (float4* plane : a->d_fplane)
-    if (plane) (void)hipFree(plane);
-  if (a->d_ftiles) (void)hipFree(a->d_ftiles);
-  for (void* p : {(void*)a->d_fa, (void*)a->d_fn, (void*)a->d_feat_tiles, (void*)a->d_gplane[0], (void*)a->d_gplane[1], (void*)a->d_mtiles,
-                  (void*)a->d_ferr})
-    if (p) (void)hipFree(p);
+  delete a; /* its device buffers go with it (DevBuf); freeing one waits for the work that uses it */
   if (prev >= 0) (void)hipSetDevice(prev);
-  delete a;
 }
 
 hrt_status hrt_accum_reset(hrt_accum* a, void* stream) {
   return hguard([&] {
     if (!a) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_reset: null accumulator"};
     DeviceGuard dg(a->device);
-    hip_check(hipMemsetAsync(a->d_acc, 0, a->n_px * sizeof(float4), (hipStream_t)stream), "hipMemsetAsync(accumulator)");
-    if (a->d_m2) hip_check(hipMemsetAsync(a->d_m2, 0, a->n_px * sizeof(float), (hipStream_t)stream), "hipMemsetAsync(noise plane)");
-    for (float4* pl : {a->d_fa, a->d_fn})
+    hip_check(hipMemsetAsync(a->d_acc.p, 0, a->n_px * sizeof(float4), (hipStream_t)stream), "hipMemsetAsync(accumulator)");
+    if (a->d_m2.p) hip_check(hipMemsetAsync(a->d_m2.p, 0, a->n_px * sizeof(float), (hipStream_t)stream), "hipMemsetAsync(noise plane)");
+    for (float4* pl : {a->d_fa.p, a->d_fn.p})
       if (pl) hip_check(hipMemsetAsync(pl, 0, a->n_px * sizeof(float4), (hipStream_t)stream), "hipMemsetAsync(feature plane)");
     a->ledger.clear();
     a->f_ledger.clear();
@@ -783,36 +814,28 @@ hrt_status hrt_accum_add_tiles(hrt_accum* a, const hrt_camera* cam, const hrt_re
 hrt_status hrt_accum_noise(hrt_accum* a, float floor, float* d_err, void* stream_, hrt_tile_noise* tiles_out) {
   return hguard([&] {
     if (!a || !tiles_out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_noise: null argument"};
-    if (!(floor > 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_noise: floor must be > 0"};
+    noise_floor(floor, "hrt_accum_noise");
     accum_usable(a);
-    if (!a->d_m2) throw HipError{HRT_ERR_STATE, "hrt_accum_noise: the accumulator was created without HRT_ACCUM_NOISE"};
+    if (!a->d_m2.p) throw HipError{HRT_ERR_STATE, "hrt_accum_noise: the accumulator was created without HRT_ACCUM_NOISE"};
     accum_holds_samples(a);
     DeviceGuard dg(a->device);
     hipStream_t stream = (hipStream_t)stream_;
     const uint32_t nt = (uint32_t)a->tiles.size();
     upload_noise_tiles(a, stream);
-    hipLaunchKernelGGL(accum_noise, dim3(nt), dim3(accum::NOISE_BLOCK), 0, stream, (const float4*)a->d_acc, (const float*)a->d_m2,
-                       (const NoiseTile*)a->d_ntiles, floor, d_err, a->d_nout);
+    hipLaunchKernelGGL(accum_noise, dim3(nt), dim3(accum::NOISE_BLOCK), 0, stream, (const float4*)a->d_acc.p, (const float*)a->d_m2.p,
+                       (const NoiseTile*)a->d_ntiles.p, floor, d_err, a->d_nout.p);
     hip_check(hipGetLastError(), "accum_noise launch");
-    std::vector<float2> rec(nt);
-    hip_check(hipMemcpyAsync(rec.data(), a->d_nout, nt * sizeof(float2), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(noise records)");
-    hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize(noise)");
-    for (uint32_t t = 0; t < nt; t++) {
-      tiles_out[t].mean = rec[t].x;
-      tiles_out[t].max = rec[t].y;
-      tiles_out[t].samples = a->ledger.samples(t);
-      tiles_out[t].chunks = a->ledger.chunks(t);
-    }
+    read_tile_noise(a, stream, tiles_out);
   });
 }
 
 hrt_status hrt_debug_accum_moments(hrt_accum* a, float* m2_out) {
   return hguard([&] {
     if (!a || !m2_out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_accum_moments: null argument"};
-    if (!a->d_m2) throw HipError{HRT_ERR_STATE, "hrt_debug_accum_moments: the accumulator was created without HRT_ACCUM_NOISE"};
+    if (!a->d_m2.p) throw HipError{HRT_ERR_STATE, "hrt_debug_accum_moments: the accumulator was created without HRT_ACCUM_NOISE"};
     DeviceGuard dg(a->device);
     hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
-    hip_check(hipMemcpy(m2_out, a->d_m2, a->n_px * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(moments)");
+    hip_check(hipMemcpy(m2_out, a->d_m2.p, a->n_px * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(moments)");
   });
 }
 
@@ -841,10 +864,10 @@ hrt_status hrt_accum_resolve_filtered(hrt_accum* a, const hrt_filter_params* f, 
   return hguard([&] {
     if (!a || !f || !d_out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_resolve_filtered: null argument"};
     accum_format(format);
-    filter_args(f);
-    filter_state(a);
+    const FilterCall c = filter_call(f);
+    filtered_state(a, c, "hrt_accum_resolve_filtered");
     DeviceGuard dg(a->device);
-    launch_filtered(a, f->iterations, f->sigma, nullptr, NO_DEMOD, format, d_out, (hipStream_t)stream);
+    launch_filtered(a, c, format, d_out, (hipStream_t)stream);
   });
 }
 
@@ -852,10 +875,9 @@ hrt_status hrt_accum_resolve_filtered_host(hrt_accum* a, const hrt_filter_params
   return hguard([&] {
     if (!a || !f || !out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_resolve_filtered_host: null argument"};
     accum_format(format);
-    filter_args(f);
-    filter_state(a);
-    resolve_to_host(a, format, out, "hipMemcpy(filtered resolve)",
-                    [&](void* d_out) { launch_filtered(a, f->iterations, f->sigma, nullptr, NO_DEMOD, format, d_out, nullptr); });
+    const FilterCall c = filter_call(f);
+    filtered_state(a, c, "hrt_accum_resolve_filtered_host");
+    resolve_to_host(a, format, out, "hipMemcpy(filtered resolve)", [&](void* d_out) { launch_filtered(a, c, format, d_out, nullptr); });
   });
 }
 
@@ -866,16 +888,15 @@ hrt_status hrt_accum_add_features(hrt_accum* a, const hrt_camera* cam, const hrt
     features_flag(a, "hrt_accum_add_features");
     const FrameIdentity id = frame_identity(cam, p);
     check_identity(a, id);
-    check_range(a->f_ledger.may_add(SampleRange{p->sample_offset, (uint64_t)p->sample_offset + p->samples}));
+    check_range(a->f_ledger.may_add(pass_range(p)));
     DeviceGuard dg(a->device);
     int cull = 0;
     bool full = false;
     const KParams kp = feature_params(a->scene, cam, p, cull, full);
-    features::launch_features(cull, full, kp, a->d_feat_tiles, (uint32_t)a->tiles.size(), a->feat_blocks, a->feat_log_bw, a->d_fa,
-                              a->d_fn, stream);
-    a->identity = id;
-    a->has_identity = true;
-    a->f_ledger.record(SampleRange{p->sample_offset, (uint64_t)p->sample_offset + p->samples}, 0);
+    features::launch_features(cull, full, kp, a->d_feat_tiles.p, (uint32_t)a->tiles.size(), a->feat_blocks, a->feat_log_bw, a->d_fa.p,
+                              a->d_fn.p, stream);
+    adopt_identity(a, id);
+    a->f_ledger.record(pass_range(p), 0);
   });
 }
 
@@ -894,7 +915,7 @@ hrt_status hrt_accum_features(hrt_accum* a, void* d_albedo, void* d_normal, void
     features_flag(a, "hrt_accum_features");
     if (feature_samples(a) == 0) throw HipError{HRT_ERR_STATE, "hrt_accum_features: the accumulator holds no feature samples"};
     DeviceGuard dg(a->device);
-    features::launch_feature_means(a->d_fa, a->d_fn, a->n_px, 1.0f / (float)feature_samples(a), d_albedo, d_normal, stream);
+    features::launch_feature_means(a->d_fa.p, a->d_fn.p, a->n_px, 1.0f / (float)feature_samples(a), d_albedo, d_normal, stream);
   });
 }
 
@@ -908,7 +929,7 @@ hrt_status hrt_accum_features_host(hrt_accum* a, float* albedo, float* normal) {
     const size_t bytes = a->n_px * sizeof(float4);
     DevBuf<float4> d_al(bytes), d_no(bytes);
     hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
-    features::launch_feature_means(a->d_fa, a->d_fn, a->n_px, 1.0f / (float)feature_samples(a), d_al.p, d_no.p, nullptr);
+    features::launch_feature_means(a->d_fa.p, a->d_fn.p, a->n_px, 1.0f / (float)feature_samples(a), d_al.p, d_no.p, nullptr);
     if (albedo) hip_check(hipMemcpy(albedo, d_al.p, bytes, hipMemcpyDeviceToHost), "hipMemcpy(albedo plane)");
     if (normal) hip_check(hipMemcpy(normal, d_no.p, bytes, hipMemcpyDeviceToHost), "hipMemcpy(normal plane)");
   });
@@ -920,8 +941,8 @@ hrt_status hrt_debug_accum_features(hrt_accum* a, float* fa_out, float* fn_out) 
     features_flag(a, "hrt_debug_accum_features");
     DeviceGuard dg(a->device);
     hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
-    hip_check(hipMemcpy(fa_out, a->d_fa, a->n_px * sizeof(float4), hipMemcpyDeviceToHost), "hipMemcpy(feature sums)");
-    hip_check(hipMemcpy(fn_out, a->d_fn, a->n_px * sizeof(float4), hipMemcpyDeviceToHost), "hipMemcpy(feature sums)");
+    hip_check(hipMemcpy(fa_out, a->d_fa.p, a->n_px * sizeof(float4), hipMemcpyDeviceToHost), "hipMemcpy(feature sums)");
+    hip_check(hipMemcpy(fn_out, a->d_fn.p, a->n_px * sizeof(float4), hipMemcpyDeviceToHost), "hipMemcpy(feature sums)");
   });
 }
 
@@ -929,10 +950,10 @@ hrt_status hrt_accum_resolve_guided(hrt_accum* a, const hrt_guided_params* g, in
   return hguard([&] {
     if (!a || !g || !d_out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_resolve_guided: null argument"};
     accum_format(format);
-    const filter::Terms K = guided_args(g);
-    guided_state(a);
+    const FilterCall c = filter_call(g);
+    filtered_state(a, c, "hrt_accum_resolve_guided");
     DeviceGuard dg(a->device);
-    launch_filtered(a, g->iterations, g->sigma, &K, NO_DEMOD, format, d_out, (hipStream_t)stream);
+    launch_filtered(a, c, format, d_out, (hipStream_t)stream);
   });
 }
 
@@ -940,10 +961,9 @@ hrt_status hrt_accum_resolve_guided_host(hrt_accum* a, const hrt_guided_params* 
   return hguard([&] {
     if (!a || !g || !out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_resolve_guided_host: null argument"};
     accum_format(format);
-    const filter::Terms K = guided_args(g);
-    guided_state(a);
-    resolve_to_host(a, format, out, "hipMemcpy(guided resolve)",
-                    [&](void* d_out) { launch_filtered(a, g->iterations, g->sigma, &K, NO_DEMOD, format, d_out, nullptr); });
+    const FilterCall c = filter_call(g);
+    filtered_state(a, c, "hrt_accum_resolve_guided_host");
+    resolve_to_host(a, format, out, "hipMemcpy(guided resolve)", [&](void* d_out) { launch_filtered(a, c, format, d_out, nullptr); });
   });
 }
 
@@ -951,11 +971,10 @@ hrt_status hrt_accum_resolve_guided_ex(hrt_accum* a, const hrt_guided_ex_params*
   return hguard([&] {
     if (!a || !g || !d_out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_resolve_guided_ex: null argument"};
     accum_format(format);
-    filter::Demod demod = NO_DEMOD;
-    const filter::Terms K = guided_ex_args(g, demod);
-    guided_state(a);
+    const FilterCall c = filter_call(g);
+    filtered_state(a, c, "hrt_accum_resolve_guided_ex");
     DeviceGuard dg(a->device);
-    launch_filtered(a, g->iterations, g->sigma, &K, demod, format, d_out, (hipStream_t)stream);
+    launch_filtered(a, c, format, d_out, (hipStream_t)stream);
   });
 }
 
@@ -963,11 +982,9 @@ hrt_status hrt_accum_resolve_guided_ex_host(hrt_accum* a, const hrt_guided_ex_pa
   return hguard([&] {
     if (!a || !g || !out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_resolve_guided_ex_host: null argument"};
     accum_format(format);
-    filter::Demod demod = NO_DEMOD;
-    const filter::Terms K = guided_ex_args(g, demod);
-    guided_state(a);
-    resolve_to_host(a, format, out, "hipMemcpy(guided resolve)",
-                    [&](void* d_out) { launch_filtered(a, g->iterations, g->sigma, &K, demod, format, d_out, nullptr); });
+    const FilterCall c = filter_call(g);
+    filtered_state(a, c, "hrt_accum_resolve_guided_ex_host");
+    resolve_to_host(a, format, out, "hipMemcpy(guided resolve)", [&](void* d_out) { launch_filtered(a, c, format, d_out, nullptr); });
   });
 }
 
@@ -975,33 +992,21 @@ hrt_status hrt_accum_noise_filtered(hrt_accum* a, const hrt_guided_ex_params* g,
                                     hrt_tile_noise* tiles_out) {
   return hguard([&] {
     if (!a || !g || !tiles_out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_noise_filtered: null argument"};
-    if (!(floor > 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_noise_filtered: floor must be > 0"};
-    filter::Demod demod = NO_DEMOD;
-    const filter::Terms K = guided_ex_args(g, demod);
-    /* no term and no flag: the variance-only filter, which reads no feature plane and asks for none */
-    const bool plain = !demod.on && K.kn == 0.0f && K.ka == 0.0f && K.kz == 0.0f;
-    if (plain) filter_state(a);
-    else guided_state(a);
+    noise_floor(floor, "hrt_accum_noise_filtered");
+    FilterCall c = filter_call(g);
+    c.guided = !variance_only(c.K, c.demod);
+    c.err_floor = floor;
+    filtered_state(a, c, "hrt_accum_noise_filtered");
     DeviceGuard dg(a->device);
     hipStream_t stream = (hipStream_t)stream_;
     if (!d_err) {
       filter_prepare(a, stream); /* the refusal of overlapping tiles comes before anything is made */
-      if (!a->d_ferr) hip_check(hipMalloc((void**)&a->d_ferr, a->n_px * sizeof(float)), "hipMalloc(filtered noise plane)");
-      d_err = a->d_ferr;
+      if (!a->d_ferr.p) a->d_ferr.alloc(a->n_px * sizeof(float), "hipMalloc(filtered noise plane)");
+      d_err = a->d_ferr.p;
     }
-    const uint32_t nt = (uint32_t)a->tiles.size();
-    launch_filtered(a, g->iterations, g->sigma, plain ? nullptr : &K, demod, filter::FORMAT_ERR, d_err, stream, floor);
-    filter::launch_err_reduce(d_err, a->d_ftiles, nt, a->d_nout, stream);
-    std::vector<float2> rec(nt);
-    hip_check(hipMemcpyAsync(rec.data(), a->d_nout, nt * sizeof(float2), hipMemcpyDeviceToHost, stream),
-              "hipMemcpyAsync(filtered noise records)");
-    hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize(filtered noise)");
-    for (uint32_t t = 0; t < nt; t++) {
-      tiles_out[t].mean = rec[t].x;
-      tiles_out[t].max = rec[t].y;
-      tiles_out[t].samples = a->ledger.samples(t);
-      tiles_out[t].chunks = a->ledger.chunks(t);
-    }
+    launch_filtered(a, c, filter::FORMAT_ERR, d_err, stream);
+    filter::launch_err_reduce(d_err, a->d_ftiles.p, (uint32_t)a->tiles.size(), a->d_nout.p, stream);
+    read_tile_noise(a, stream, tiles_out);
   });
 }
 
@@ -1010,17 +1015,8 @@ hrt_status hrt_accum_merge(hrt_accum* dst, const hrt_accum* src, void* stream) {
     if (!dst || !src || dst == src) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_merge: null argument, or an accumulator into itself"};
     accum_usable(dst);
     accum_usable(src);
-    if ((dst->d_m2 != nullptr) != (src->d_m2 != nullptr))
-      throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_merge: one accumulator keeps a noise plane (HRT_ACCUM_NOISE), the other none"};
-    accum_uniform(dst, HRT_ERR_UNSUPPORTED, "hrt_accum_merge: the accumulator's tiles hold different passes");
-    accum_uniform(src, HRT_ERR_UNSUPPORTED, "hrt_accum_merge: the accumulator's tiles hold different passes");
-    if (dst->device != src->device || dst->width != src->width || dst->height != src->height ||
-        dst->tiles.size() != src->tiles.size() ||
-        memcmp(dst->tiles.data(), src->tiles.data(), dst->tiles.size() * sizeof(hrt_tile)) != 0)
-      throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_merge: the accumulators differ in device, image size or tiles"};
-    if ((dst->d_fa != nullptr) != (src->d_fa != nullptr))
-      throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_merge: one accumulator keeps feature planes (HRT_ACCUM_FEATURES), the other none"};
-    const bool feats = src->d_fa && !src->f_ledger.empty();
+    merge_compatible(dst, src, "hrt_accum_merge", true);
+    const bool feats = src->d_fa.p && !src->f_ledger.empty();
     if (src->ledger.empty() && !feats) return;
     check_identity(dst, src->identity);
     if (!src->ledger.empty())
@@ -1029,23 +1025,21 @@ hrt_status hrt_accum_merge(hrt_accum* dst, const hrt_accum* src, void* stream) {
       for (const SampleRange& r : *src->f_ledger.ranges()) check_range(dst->f_ledger.may_add(r));
     DeviceGuard dg(dst->device);
     if (feats) {
-      features::launch_feature_merge(dst->d_fa, dst->d_fn, src->d_fa, src->d_fn, dst->n_px, stream);
+      features::launch_feature_merge(dst->d_fa.p, dst->d_fn.p, src->d_fa.p, src->d_fn.p, dst->n_px, stream);
       dst->f_ledger.merge(src->f_ledger);
-      dst->identity = src->identity;
-      dst->has_identity = true;
+      adopt_identity(dst, src->identity);
     }
     if (src->ledger.empty()) return;
-    hipLaunchKernelGGL(accum_merge, dim3(stream_blocks(dst->n_px)), dim3(256), 0, (hipStream_t)stream, dst->d_acc,
-                       (const float4*)src->d_acc, dst->n_px);
+    hipLaunchKernelGGL(accum_merge, dim3(stream_blocks(dst->n_px)), dim3(256), 0, (hipStream_t)stream, dst->d_acc.p,
+                       (const float4*)src->d_acc.p, dst->n_px);
     hip_check(hipGetLastError(), "accum_merge launch");
-    if (dst->d_m2) {
-      hipLaunchKernelGGL(accum_merge_m2, dim3(stream_blocks(dst->n_px)), dim3(256), 0, (hipStream_t)stream, dst->d_m2,
-                         (const float*)src->d_m2, dst->n_px);
+    if (dst->d_m2.p) {
+      hipLaunchKernelGGL(accum_merge_m2, dim3(stream_blocks(dst->n_px)), dim3(256), 0, (hipStream_t)stream, dst->d_m2.p,
+                         (const float*)src->d_m2.p, dst->n_px);
       hip_check(hipGetLastError(), "accum_merge_m2 launch");
     }
     dst->ledger.merge(src->ledger);
-    dst->identity = src->identity;
-    dst->has_identity = true;
+    adopt_identity(dst, src->identity);
   });
 }
 
@@ -1064,7 +1058,7 @@ hrt_status hrt_accum_download(hrt_accum* a, float* sums, uint32_t* ranges, uint3
     }
     DeviceGuard dg(a->device);
     hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
-    hip_check(hipMemcpy(sums, a->d_acc, a->n_px * sizeof(float4), hipMemcpyDeviceToHost), "hipMemcpy(download)");
+    hip_check(hipMemcpy(sums, a->d_acc.p, a->n_px * sizeof(float4), hipMemcpyDeviceToHost), "hipMemcpy(download)");
   });
 }
 
@@ -1073,7 +1067,7 @@ hrt_status hrt_accum_upload(hrt_accum* a, const hrt_camera* cam, const hrt_rende
   return hguard([&] {
     if (!a || !cam || !p || !sums || (!ranges && n_ranges)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_upload: null argument"};
     accum_usable(a);
-    if (a->d_m2) throw HipError{HRT_ERR_UNSUPPORTED, "hrt_accum_upload: the noise plane of a HRT_ACCUM_NOISE accumulator does not travel"};
+    if (a->d_m2.p) throw HipError{HRT_ERR_UNSUPPORTED, "hrt_accum_upload: the noise plane of a HRT_ACCUM_NOISE accumulator does not travel"};
     accum_uniform(a, HRT_ERR_UNSUPPORTED, "hrt_accum_upload: the accumulator's tiles hold different passes");
     const FrameIdentity id = frame_identity(cam, p);
     check_identity(a, id);
@@ -1088,16 +1082,15 @@ hrt_status hrt_accum_upload(hrt_accum* a, const hrt_camera* cam, const hrt_rende
     DeviceGuard dg(a->device);
     hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
     if (a->ledger.empty()) { /* no samples: the sums as they are */
-      hip_check(hipMemcpy(a->d_acc, sums, a->n_px * sizeof(float4), hipMemcpyHostToDevice), "hipMemcpy(upload)");
+      hip_check(hipMemcpy(a->d_acc.p, sums, a->n_px * sizeof(float4), hipMemcpyHostToDevice), "hipMemcpy(upload)");
     } else {
       DevBuf<float4> tmp(a->n_px * sizeof(float4));
       hip_check(hipMemcpy(tmp.p, sums, a->n_px * sizeof(float4), hipMemcpyHostToDevice), "hipMemcpy(upload)");
-      hipLaunchKernelGGL(accum_merge, dim3(stream_blocks(a->n_px)), dim3(256), 0, nullptr, a->d_acc, (const float4*)tmp.p, a->n_px);
+      hipLaunchKernelGGL(accum_merge, dim3(stream_blocks(a->n_px)), dim3(256), 0, nullptr, a->d_acc.p, (const float4*)tmp.p, a->n_px);
       hip_check(hipGetLastError(), "accum_merge launch");
       hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
     }
-    a->identity = id;
-    a->has_identity = true;
+    adopt_identity(a, id);
     a->ledger = held;
   });
 }
@@ -1107,8 +1100,8 @@ hrt_status hrt_accum_merge_tiles(hrt_accum* dst, const hrt_accum* src, void* str
     if (!dst || !src || dst == src) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_merge_tiles: null argument, or an accumulator into itself"};
     accum_usable(dst);
     accum_usable(src);
-    merge_compatible(dst, src, "hrt_accum_merge_tiles");
-    const bool feats = src->d_fa && !src->f_ledger.empty();
+    merge_compatible(dst, src, "hrt_accum_merge_tiles", false);
+    const bool feats = src->d_fa.p && !src->f_ledger.empty();
     if (src->ledger.empty() && !feats) return;
     check_identity(dst, src->identity);
     if (!dst->ledger.may_merge(src->ledger))
@@ -1126,29 +1119,27 @@ hrt_status hrt_accum_merge_tiles(hrt_accum* dst, const hrt_accum* src, void* str
       sel.push_back(MergeTile{dst->tile_off[t], n, (uint32_t)n_sel, 0u});
       n_sel += n;
     }
-    if (!sel.empty() && !dst->d_mtiles) hip_check(hipMalloc((void**)&dst->d_mtiles, nt * sizeof(MergeTile)), "hipMalloc(merge tiles)");
+    if (!sel.empty() && !dst->d_mtiles.p) dst->d_mtiles.alloc(nt * sizeof(MergeTile), "hipMalloc(merge tiles)");
     if (feats) {
-      features::launch_feature_merge(dst->d_fa, dst->d_fn, src->d_fa, src->d_fn, dst->n_px, stream);
+      features::launch_feature_merge(dst->d_fa.p, dst->d_fn.p, src->d_fa.p, src->d_fn.p, dst->n_px, stream);
       dst->f_ledger.merge(src->f_ledger);
-      dst->identity = src->identity;
-      dst->has_identity = true;
+      adopt_identity(dst, src->identity);
     }
     if (sel.empty()) return;
     dst->h_mtiles.swap(sel); /* stays alive with the accumulator, as h_ntiles does */
     const uint32_t n_tiles = (uint32_t)dst->h_mtiles.size();
-    hip_check(hipMemcpyAsync(dst->d_mtiles, dst->h_mtiles.data(), n_tiles * sizeof(MergeTile), hipMemcpyHostToDevice, (hipStream_t)stream),
+    hip_check(hipMemcpyAsync(dst->d_mtiles.p, dst->h_mtiles.data(), n_tiles * sizeof(MergeTile), hipMemcpyHostToDevice, (hipStream_t)stream),
               "hipMemcpyAsync(merge tiles)");
-    if (dst->d_m2)
-      hipLaunchKernelGGL((accum_merge_tiles<true>), dim3(stream_blocks(n_sel)), dim3(256), 0, (hipStream_t)stream, dst->d_acc,
-                         (const float4*)src->d_acc, dst->d_m2, (const float*)src->d_m2, (const MergeTile*)dst->d_mtiles, n_tiles, (size_t)n_sel);
+    if (dst->d_m2.p)
+      hipLaunchKernelGGL((accum_merge_tiles<true>), dim3(stream_blocks(n_sel)), dim3(256), 0, (hipStream_t)stream, dst->d_acc.p,
+                         (const float4*)src->d_acc.p, dst->d_m2.p, (const float*)src->d_m2.p, (const MergeTile*)dst->d_mtiles.p, n_tiles, (size_t)n_sel);
     else
-      hipLaunchKernelGGL((accum_merge_tiles<false>), dim3(stream_blocks(n_sel)), dim3(256), 0, (hipStream_t)stream, dst->d_acc,
-                         (const float4*)src->d_acc, (float*)nullptr, (const float*)nullptr, (const MergeTile*)dst->d_mtiles, n_tiles,
+      hipLaunchKernelGGL((accum_merge_tiles<false>), dim3(stream_blocks(n_sel)), dim3(256), 0, (hipStream_t)stream, dst->d_acc.p,
+                         (const float4*)src->d_acc.p, (float*)nullptr, (const float*)nullptr, (const MergeTile*)dst->d_mtiles.p, n_tiles,
                          (size_t)n_sel);
     hip_check(hipGetLastError(), "accum_merge_tiles launch");
     dst->ledger.merge_tiles(src->ledger);
-    dst->identity = src->identity;
-    dst->has_identity = true;
+    adopt_identity(dst, src->identity);
   });
 }
 
@@ -1164,11 +1155,11 @@ hrt_status hrt_accum_snapshot(hrt_accum* a, void* out, uint64_t cap, uint64_t* s
     DeviceGuard dg(a->device);
     hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
     snapshot::encode_head(s, b);
-    hip_check(hipMemcpy(b + s.off_sums, a->d_acc, a->n_px * sizeof(float4), hipMemcpyDeviceToHost), "hipMemcpy(snapshot sums)");
-    if (a->d_m2) hip_check(hipMemcpy(b + s.off_m2, a->d_m2, a->n_px * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(snapshot m2)");
-    if (a->d_fa) {
-      hip_check(hipMemcpy(b + s.off_fa, a->d_fa, a->n_px * sizeof(float4), hipMemcpyDeviceToHost), "hipMemcpy(snapshot fa)");
-      hip_check(hipMemcpy(b + s.off_fn, a->d_fn, a->n_px * sizeof(float4), hipMemcpyDeviceToHost), "hipMemcpy(snapshot fn)");
+    hip_check(hipMemcpy(b + s.off_sums, a->d_acc.p, a->n_px * sizeof(float4), hipMemcpyDeviceToHost), "hipMemcpy(snapshot sums)");
+    if (a->d_m2.p) hip_check(hipMemcpy(b + s.off_m2, a->d_m2.p, a->n_px * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(snapshot m2)");
+    if (a->d_fa.p) {
+      hip_check(hipMemcpy(b + s.off_fa, a->d_fa.p, a->n_px * sizeof(float4), hipMemcpyDeviceToHost), "hipMemcpy(snapshot fa)");
+      hip_check(hipMemcpy(b + s.off_fn, a->d_fn.p, a->n_px * sizeof(float4), hipMemcpyDeviceToHost), "hipMemcpy(snapshot fn)");
     }
     snapshot::zero_pads(s, b);
     snapshot::seal(s, b);
@@ -1194,11 +1185,11 @@ hrt_status hrt_accum_restore(hrt_accum* a, const void* blob, uint64_t size) {
     DeviceGuard dg(a->device);
     hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize"); /* a reset's memsets, on whatever stream */
     try {
-      hip_check(hipMemcpy(a->d_acc, b + s.off_sums, a->n_px * sizeof(float4), hipMemcpyHostToDevice), "hipMemcpy(restore sums)");
-      if (a->d_m2) hip_check(hipMemcpy(a->d_m2, b + s.off_m2, a->n_px * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(restore m2)");
-      if (a->d_fa) {
-        hip_check(hipMemcpy(a->d_fa, b + s.off_fa, a->n_px * sizeof(float4), hipMemcpyHostToDevice), "hipMemcpy(restore fa)");
-        hip_check(hipMemcpy(a->d_fn, b + s.off_fn, a->n_px * sizeof(float4), hipMemcpyHostToDevice), "hipMemcpy(restore fn)");
+      hip_check(hipMemcpy(a->d_acc.p, b + s.off_sums, a->n_px * sizeof(float4), hipMemcpyHostToDevice), "hipMemcpy(restore sums)");
+      if (a->d_m2.p) hip_check(hipMemcpy(a->d_m2.p, b + s.off_m2, a->n_px * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(restore m2)");
+      if (a->d_fa.p) {
+        hip_check(hipMemcpy(a->d_fa.p, b + s.off_fa, a->n_px * sizeof(float4), hipMemcpyHostToDevice), "hipMemcpy(restore fa)");
+        hip_check(hipMemcpy(a->d_fn.p, b + s.off_fn, a->n_px * sizeof(float4), hipMemcpyHostToDevice), "hipMemcpy(restore fn)");
       }
       hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
     } catch (...) {
@@ -1206,7 +1197,7 @@ hrt_status hrt_accum_restore(hrt_accum* a, const void* blob, uint64_t size) {
       throw;
     }
     a->ledger = AccumLedger(a->tiles.size(), std::move(s.records));
-    if (a->d_fa) {
+    if (a->d_fa.p) {
       std::vector<AccumLedger::Record> fr(1);
       fr[0].ranges = std::move(s.f_ranges);
       a->f_ledger = AccumLedger(a->tiles.size(), std::move(fr));
@@ -1278,7 +1269,7 @@ hrt_status hrt_debug_noise(int32_t on_device, const float* partial, const uint32
       throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_noise: bad argument"};
     for (uint32_t c = 0; c < n_chunks; c++)
       if (sizes[c] == 0) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_noise: an empty chunk"};
-    if (!(floor > 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_noise: floor must be > 0"};
+    noise_floor(floor, "hrt_debug_noise");
     const NoiseTile T = noise_tile(0, n, samples, chunks);
     const G::TileDev map{0, 0, n, 1, (n + 7) / 8, 0, 0, 0}; /* one tile: the launch's pixels onto themselves */
     if (!on_device) {
@@ -1311,6 +1302,16 @@ hrt_status hrt_debug_noise(int32_t on_device, const float* partial, const uint32
   });
 }
 
+/* the checks the four hrt_debug_* raster entry points share: the arguments and the raster's size, and the terms */
+static void debug_raster_args(const char* who, bool arguments, uint32_t width, uint32_t height) {
+  if (!arguments || width == 0 || height == 0 || width > 65535 || height > 65535)
+    throw HipError{HRT_ERR_INVALID_ARG, std::string(who) + ": null argument or no tiles, or a width or height outside [1, 65535]"};
+}
+static filter::Terms debug_terms(const char* who, float kn, float ka, float kz) {
+  if (!(kn >= 0.0f) || !(ka >= 0.0f) || !(kz >= 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, std::string(who) + ": a negative or NaN term"};
+  return filter::Terms{kn, ka, kz};
+}
+
 /* hrt_debug_filter, hrt_debug_guided and hrt_debug_guided_ex after their checks; albedo and normal null: the plain
  * filter */
 static void debug_atrous(int32_t on_device, const float* raster, const float* albedo, const float* normal, uint32_t width,
@@ -1332,10 +1333,8 @@ static void debug_atrous(int32_t on_device, const float* raster, const float* al
 hrt_status hrt_debug_filter(int32_t on_device, const float* raster, uint32_t width, uint32_t height, uint32_t iterations,
                             float sigma, float* out) {
   return hguard([&] {
-    if (!raster || !out || width == 0 || height == 0 || width > 65535 || height > 65535)
-      throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_filter: null argument, or a width or height outside [1, 65535]"};
-    const hrt_filter_params f{iterations, sigma};
-    filter_args(&f);
+    debug_raster_args("hrt_debug_filter", raster && out, width, height);
+    filter_args(iterations, sigma);
     debug_atrous(on_device, raster, nullptr, nullptr, width, height, iterations, sigma, filter::Terms{}, NO_DEMOD, out);
   });
 }
@@ -1343,12 +1342,10 @@ hrt_status hrt_debug_filter(int32_t on_device, const float* raster, uint32_t wid
 hrt_status hrt_debug_guided(int32_t on_device, const float* raster, const float* albedo, const float* normal, uint32_t width,
                             uint32_t height, uint32_t iterations, float sigma, float kn, float ka, float kz, float* out) {
   return hguard([&] {
-    if (!raster || !albedo || !normal || !out || width == 0 || height == 0 || width > 65535 || height > 65535)
-      throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_guided: null argument, or a width or height outside [1, 65535]"};
-    const hrt_filter_params f{iterations, sigma};
-    filter_args(&f);
-    if (!(kn >= 0.0f) || !(ka >= 0.0f) || !(kz >= 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_guided: a negative or NaN term"};
-    debug_atrous(on_device, raster, albedo, normal, width, height, iterations, sigma, filter::Terms{kn, ka, kz}, NO_DEMOD, out);
+    debug_raster_args("hrt_debug_guided", raster && albedo && normal && out, width, height);
+    filter_args(iterations, sigma);
+    const filter::Terms K = debug_terms("hrt_debug_guided", kn, ka, kz);
+    debug_atrous(on_device, raster, albedo, normal, width, height, iterations, sigma, K, NO_DEMOD, out);
   });
 }
 
@@ -1356,13 +1353,11 @@ hrt_status hrt_debug_guided_ex(int32_t on_device, const float* raster, const flo
                                uint32_t height, uint32_t iterations, float sigma, float kn, float ka, float kz, uint32_t flags,
                                float albedo_floor, float* out) {
   return hguard([&] {
-    if (!raster || !albedo || !normal || !out || width == 0 || height == 0 || width > 65535 || height > 65535)
-      throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_guided_ex: null argument, or a width or height outside [1, 65535]"};
-    const hrt_filter_params f{iterations, sigma};
-    filter_args(&f);
-    if (!(kn >= 0.0f) || !(ka >= 0.0f) || !(kz >= 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_guided_ex: a negative or NaN term"};
+    debug_raster_args("hrt_debug_guided_ex", raster && albedo && normal && out, width, height);
+    filter_args(iterations, sigma);
+    const filter::Terms K = debug_terms("hrt_debug_guided_ex", kn, ka, kz);
     const filter::Demod demod = guided_ex_option(flags, albedo_floor);
-    debug_atrous(on_device, raster, albedo, normal, width, height, iterations, sigma, filter::Terms{kn, ka, kz}, demod, out);
+    debug_atrous(on_device, raster, albedo, normal, width, height, iterations, sigma, K, demod, out);
   });
 }
 
@@ -1371,36 +1366,26 @@ hrt_status hrt_debug_noise_filtered(int32_t on_device, const float* raster, cons
                                     float albedo_floor, float floor, const hrt_tile* tiles, uint32_t n_tiles, float* err_out,
                                     float* mean_max_out) {
   return hguard([&] {
-    if (!raster || !tiles || n_tiles == 0 || !err_out || !mean_max_out || width == 0 || height == 0 || width > 65535 || height > 65535)
-      throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_noise_filtered: null argument, no tiles, or a width or height outside [1, 65535]"};
-    const hrt_filter_params f{iterations, sigma};
-    filter_args(&f);
-    if (!(kn >= 0.0f) || !(ka >= 0.0f) || !(kz >= 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_noise_filtered: a negative or NaN term"};
+    debug_raster_args("hrt_debug_noise_filtered", raster && tiles && n_tiles != 0 && err_out && mean_max_out, width, height);
+    filter_args(iterations, sigma);
+    const filter::Terms K = debug_terms("hrt_debug_noise_filtered", kn, ka, kz);
     const filter::Demod demod = guided_ex_option(flags, albedo_floor);
-    if (!(floor > 0.0f)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_noise_filtered: floor must be > 0"};
-    const bool plain = !demod.on && kn == 0.0f && ka == 0.0f && kz == 0.0f;
+    noise_floor(floor, "hrt_debug_noise_filtered");
+    const bool plain = variance_only(K, demod);
     if (!plain && (!albedo || !normal)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_noise_filtered: a term or the flag needs the feature rasters"};
     /* the tiles lie inside the raster, overlap nowhere and cover present pixels only */
     const size_t area = (size_t)width * height;
-    std::vector<bool> covered(area, false);
+    const TileCover cover = tile_cover(tiles, n_tiles, 0, 0, width, height, [&](size_t k) { return raster[4 * k + 3] < 0.0f; });
+    if (cover == TileCover::OUTSIDE) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_noise_filtered: a tile is empty or leaves the raster"};
+    if (cover == TileCover::OVERLAP) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_noise_filtered: tiles overlap or cover an absent pixel"};
     std::vector<filter::FilterTile> ft(n_tiles);
     size_t off = 0, blocks = 0;
     for (uint32_t t = 0; t < n_tiles; t++) {
       const hrt_tile& T = tiles[t];
-      if (T.w == 0 || T.h == 0 || T.x >= width || T.y >= height || T.w > width - T.x || T.h > height - T.y)
-        throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_noise_filtered: a tile is empty or leaves the raster"};
-      for (uint32_t y = T.y; y < T.y + T.h; y++)
-        for (uint32_t x = T.x; x < T.x + T.w; x++) {
-          const size_t k = (size_t)y * width + x;
-          if (covered[k] || raster[4 * k + 3] < 0.0f)
-            throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_noise_filtered: tiles overlap or cover an absent pixel"};
-          covered[k] = true;
-        }
       ft[t] = filter::FilterTile{T.x, T.y, T.w, T.h, (uint32_t)off, (uint32_t)blocks, 0.0f, 0.0f};
       off += (size_t)T.w * T.h;
       blocks += filter::tile_blocks(T.w, T.h);
     }
-    const filter::Terms K{kn, ka, kz};
     const float* al = plain ? nullptr : albedo;
     const float* no = plain ? nullptr : normal;
     if (!on_device) {

@@ -3,6 +3,7 @@
 #pragma once
 #include <algorithm>
 #include <new>
+#include <utility>
 
 #include "kernel_common.h"
 
@@ -36,16 +37,30 @@ hrt_status hguard(F&& f) {
   }
 }
 
-/* a device buffer freed on every exit path (the debug entry points throw through hip_check), filled from src if given */
+/* An owned device buffer, freed with its owner: on every exit path of a call (the debug entry points throw through
+ * hip_check), or with the accumulator that keeps it as a member.  Empty until alloc() (`what`: the hip_check label), or
+ * made at once and filled from src if given.  The free is on the calling thread's current device and its result is
+ * ignored. */
 template <typename T>
 struct DevBuf {
   T* p = nullptr;
-  explicit DevBuf(size_t bytes, const void* src = nullptr) {
-    hip_check(hipMalloc((void**)&p, bytes), "hipMalloc(debug)");
+  DevBuf() = default;
+  explicit DevBuf(size_t bytes, const void* src = nullptr) : DevBuf() { /* delegating: a throw below still frees p */
+    alloc(bytes, "hipMalloc(debug)");
     if (src) hip_check(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice), "hipMemcpy");
+  }
+  void alloc(size_t bytes, const char* what) {
+    DevBuf fresh;
+    hip_check(hipMalloc((void**)&fresh.p, bytes), what);
+    *this = std::move(fresh);
   }
   ~DevBuf() {
     if (p) (void)hipFree(p);
+  }
+  DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    std::swap(p, o.p); /* o frees what this held */
+    return *this;
   }
   DevBuf(const DevBuf&) = delete;
   DevBuf& operator=(const DevBuf&) = delete;

@@ -761,6 +761,25 @@ class Accumulator:
             return flat.reshape(self.tiles[0][3], self.tiles[0][2], 4)
         return flat.reshape(self.n_pixels, 4)
 
+    def _device_buffer(self, n: int, dtype):
+        """(buffer, stream): an empty torch buffer of n elements on the scene's device, and that device's current stream."""
+        import torch
+
+        dev = torch.device("cuda", self.scene.device if self.scene.device >= 0 else torch.cuda.current_device())
+        return torch.empty(n, dtype=dtype, device=dev), torch.cuda.current_stream(dev)
+
+    def _tile_noise(self, call, error_map: bool):
+        """The tail `noise` and `noise_filtered` share: call(d_err, stream, records), with a device error map if asked for."""
+        rec = (TileNoise * len(self.tiles))()
+        if not error_map:
+            _check(call(None, None, ctypes.cast(rec, ctypes.c_void_p)))
+            return list(rec)
+        import torch
+
+        buf, stream = self._device_buffer(self.n_pixels, torch.float32)
+        _check(call(ctypes.c_void_p(buf.data_ptr()), ctypes.c_void_p(stream.cuda_stream), ctypes.cast(rec, ctypes.c_void_p)))
+        return list(rec), buf.cpu().numpy()
+
     def add(self, cam: Camera, p: RenderParams, stats: bool = False, preview=None, tiles=None):
         """Render samples [p.sample_offset, p.sample_offset + p.samples) of every pixel and add them.  preview
         ("f32" / "rgba8", or True for "f32"): also return the frame after this pass, resolved by the kernel that adds
@@ -781,9 +800,7 @@ class Accumulator:
         import torch
 
         fmt = "f32" if preview is True else preview
-        dev = torch.device("cuda", self.scene.device if self.scene.device >= 0 else torch.cuda.current_device())
-        buf = torch.empty(self.n_pixels * 4, dtype=torch.float32 if fmt == "f32" else torch.uint8, device=dev)
-        stream = torch.cuda.current_stream(dev)
+        buf, stream = self._device_buffer(self.n_pixels * 4, torch.float32 if fmt == "f32" else torch.uint8)
         _check(load().hrt_accum_add_resolve(self.h, ctypes.byref(cam), ctypes.byref(p), _ACCUM_FORMATS[fmt],
                                             ctypes.c_void_p(buf.data_ptr()), ctypes.c_void_p(stream.cuda_stream), sp))
         stream.synchronize()
@@ -806,18 +823,7 @@ class Accumulator:
     def noise(self, floor: float = 0.05, error_map: bool = False):
         """hrt_accum_noise: one TileNoise per tile (mean and max of the per-pixel relative standard error, samples,
         chunks); with error_map also the per-pixel errors as float32 (n_pixels,), packed as the tiles are."""
-        rec = (TileNoise * len(self.tiles))()
-        if not error_map:
-            _check(load().hrt_accum_noise(self.h, float(floor), None, None, ctypes.cast(rec, ctypes.c_void_p)))
-            return list(rec)
-        import torch
-
-        dev = torch.device("cuda", self.scene.device if self.scene.device >= 0 else torch.cuda.current_device())
-        buf = torch.empty(self.n_pixels, dtype=torch.float32, device=dev)
-        stream = torch.cuda.current_stream(dev)
-        _check(load().hrt_accum_noise(self.h, float(floor), ctypes.c_void_p(buf.data_ptr()), ctypes.c_void_p(stream.cuda_stream),
-                                      ctypes.cast(rec, ctypes.c_void_p)))
-        return list(rec), buf.cpu().numpy()
+        return self._tile_noise(lambda d_err, stream, rec: load().hrt_accum_noise(self.h, float(floor), d_err, stream, rec), error_map)
 
     def moments(self) -> np.ndarray:
         """The noise plane m2 as float32 (n_pixels,) (hrt_debug_accum_moments)."""
@@ -892,18 +898,8 @@ class Accumulator:
         guide=False (the default) switches every feature term off, which with demodulate=False is resolve(denoise=...)'s
         frame and needs no feature planes.  Returns what `noise` returns."""
         g = self._noise_filtered_params(denoise, guide, demodulate)
-        rec = (TileNoise * len(self.tiles))()
-        if not error_map:
-            _check(load().hrt_accum_noise_filtered(self.h, ctypes.byref(g), float(floor), None, None, ctypes.cast(rec, ctypes.c_void_p)))
-            return list(rec)
-        import torch
-
-        dev = torch.device("cuda", self.scene.device if self.scene.device >= 0 else torch.cuda.current_device())
-        buf = torch.empty(self.n_pixels, dtype=torch.float32, device=dev)
-        stream = torch.cuda.current_stream(dev)
-        _check(load().hrt_accum_noise_filtered(self.h, ctypes.byref(g), float(floor), ctypes.c_void_p(buf.data_ptr()),
-                                               ctypes.c_void_p(stream.cuda_stream), ctypes.cast(rec, ctypes.c_void_p)))
-        return list(rec), buf.cpu().numpy()
+        return self._tile_noise(
+            lambda d_err, stream, rec: load().hrt_accum_noise_filtered(self.h, ctypes.byref(g), float(floor), d_err, stream, rec), error_map)
 
     def refine_filtered(self, cam: Camera, p: RenderParams, target: float, pass_spp: int, max_spp: int, floor: float = 0.05,
                         denoise=True, guide=False, demodulate=False, min_spp: int = 0, on_pass=None, resume: bool = False):

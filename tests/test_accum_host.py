@@ -148,3 +148,48 @@ def test_null_handles_are_invalid_arguments():
     assert L.hrt_accum_resolve_host(None, 0, None) == hrt.ERR_INVALID_ARG
     assert L.hrt_accum_merge(None, None, None) == hrt.ERR_INVALID_ARG
     assert L.hrt_debug_accumulate(0, None, 1, 1, None, 1, -1, None) == hrt.ERR_INVALID_ARG
+
+
+def test_every_entry_point_refuses_a_null_accumulator():
+    """The accumulator entry points test_null_handles_are_invalid_arguments leaves out: a null accumulator (or scene, or
+    blob) is refused before any device call, whatever else is passed."""
+    L = hrt.load()
+    s = hrt.preset("two_spheres", 1)
+    cam, p = ctypes.byref(hrt.preset_camera(s.info, 16, 16)), ctypes.byref(hrt.params(16, 16, 2))
+    f, g, x = ctypes.byref(hrt.filter_params()), ctypes.byref(hrt.guided_params()), ctypes.byref(hrt.guided_ex_params())
+    arr = np.zeros(16 * 16 * 4, np.float32)
+    buf = arr.ctypes.data
+    n64, n32, out = ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_void_p()
+    tile = ctypes.cast((hrt.Tile * 1)(hrt.Tile(0, 0, 16, 16)), ctypes.c_void_p)
+    calls = {
+        "create_ex": lambda: L.hrt_accum_create_ex(None, 16, 16, tile, 1, 0, ctypes.byref(out)),
+        "add": lambda: L.hrt_accum_add(None, cam, p, None, None),
+        "add_resolve": lambda: L.hrt_accum_add_resolve(None, cam, p, 0, buf, None, None),
+        "add_tiles": lambda: L.hrt_accum_add_tiles(None, cam, p, buf, 1, None, None),
+        "tile_samples": lambda: L.hrt_accum_tile_samples(None, buf),
+        "noise": lambda: L.hrt_accum_noise(None, 0.05, None, None, buf),
+        "debug_accum_moments": lambda: L.hrt_debug_accum_moments(None, buf),
+        "resolve": lambda: L.hrt_accum_resolve(None, 0, buf, None),
+        "resolve_filtered": lambda: L.hrt_accum_resolve_filtered(None, f, 0, buf, None),
+        "resolve_filtered_host": lambda: L.hrt_accum_resolve_filtered_host(None, f, 0, buf),
+        "add_features": lambda: L.hrt_accum_add_features(None, cam, p, None),
+        "feature_samples": lambda: L.hrt_accum_feature_samples(None, ctypes.byref(n64)),
+        "features": lambda: L.hrt_accum_features(None, buf, buf, None),
+        "features_host": lambda: L.hrt_accum_features_host(None, buf, buf),
+        "debug_accum_features": lambda: L.hrt_debug_accum_features(None, buf, buf),
+        "resolve_guided": lambda: L.hrt_accum_resolve_guided(None, g, 0, buf, None),
+        "resolve_guided_host": lambda: L.hrt_accum_resolve_guided_host(None, g, 0, buf),
+        "resolve_guided_ex": lambda: L.hrt_accum_resolve_guided_ex(None, x, 0, buf, None),
+        "resolve_guided_ex_host": lambda: L.hrt_accum_resolve_guided_ex_host(None, x, 0, buf),
+        "noise_filtered": lambda: L.hrt_accum_noise_filtered(None, x, 0.05, None, None, buf),
+        "merge_tiles": lambda: L.hrt_accum_merge_tiles(None, None, None),
+        "download": lambda: L.hrt_accum_download(None, None, None, 0, ctypes.byref(n32)),
+        "upload": lambda: L.hrt_accum_upload(None, cam, p, buf, None, 0),
+        "snapshot": lambda: L.hrt_accum_snapshot(None, None, 0, ctypes.byref(n64)),
+        "restore": lambda: L.hrt_accum_restore(None, buf, 16),
+        "snapshot_info": lambda: L.hrt_accum_snapshot_info(None, 0, ctypes.byref(hrt.SnapshotInfo()), None, 0),
+    }
+    for name, call in calls.items():
+        assert call() == hrt.ERR_INVALID_ARG, name
+    assert not out.value
+    s.close()
