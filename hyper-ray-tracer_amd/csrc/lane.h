@@ -110,7 +110,7 @@ struct KParams {
  * class alone (never on the tile split), so every split sums a pixel's samples in the same chunks.  A
  * chunk should be long enough that claiming it and writing its partial sum are cheap next to its
  * samples, and short enough that the launch's last items (run with the device mostly idle) end soon:
- * - sphere scenes (render_basic_kernel: block claims, short passes): >= 16 samples, <= 32 chunks;
+ * - sphere scenes (render_basic_kernel: block claims, cheap passes): >= 16 samples, <= 32 chunks;
  * - general scenes: <= 8 chunks of >= 32 samples; when the main node stream is deep (> 1024 nodes:
  *   expensive samples of very uneven length) <= 64 chunks of >= 1 sample.
  * Measured: Earth+Perlin 1000 spp 11447 Mrays/s with 8 chunks vs 9703 with 32;

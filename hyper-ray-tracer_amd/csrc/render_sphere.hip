@@ -103,7 +103,6 @@ void render_basic_kernel(KParams P) {
   bool has_item = false, exhausted = false;
   bool walking = false; /* a segment is in flight (walk running, or finished and waiting to shade) */
   bool setup = false;   /* the lane's next segment needs its ray set up (a new sample, or a scattered ray) */
-  bool short_prev = false; /* LISTS: the last pass was a short one (wave-uniform) */
   Item it{0u, 0u, 0u, 0u};
   WaveBlock wb{0u, 0u};
 #if HRT_CLAIM_BLOCKS
@@ -138,7 +137,86 @@ void render_basic_kernel(KParams P) {
   };
   stamp(-1);
 
+  /* a finished segment: its walk has run out with nothing parked or pending, or there was none to run */
+  auto finished = [&]() { return walking && node >= end && !walk_pend<C16>(node) && (!SPEC || pend == G::NONE); };
+  /* LISTS: a finished segment that ends its path with no shading left to do: a miss (the walk ran, no winner), the
+   * untraced segment of a max_depth 0 path (node NONE from the ray setup, no winner), or a hit whose shading
+   * ended the path in the last pass (node NONE, set there, with the winner kept) */
+  auto path_over = [&]() { return finished() && (winner == G::NONE || node == G::NONE); };
+  /* one pass through the ray setup (1/d, d.d) for the lanes that need it */
+  auto setup_rays = [&]() {
+    if (setup) {
+#if HRT_RAY_REDERIVE_SPHERE
+      r.o = ps.ro;
+      r.d = ps.rd;
+      set_time(r, ps.rtime, P); /* a scattered ray keeps the sample's shutter time */
+#else
+      set_ray(r, ps.ro, ps.rd, ps.rtime, P);
+#endif
+      closest = inf;
+      winner = G::NONE;
+      node = ps.depth_left == 0 ? G::NONE : root; /* max_depth 0: black without a world.hit (:478-480) */
+      setup = false;
+    }
+#if HRT_RAY_REDERIVE_SPHERE
+    set_dir(r, r.o, r.d); /* every lane: dead across shading (kernel_common.h) */
+#endif
+  };
+
+  /* LISTS: shade the finished hits, the walked and the listed ones together: ONE execution per pass
+   * (application.rs:483-494) */
+  auto shade_hits = [&]() {
+    stamp(0);
+    const bool hit = finished() && winner != G::NONE && node != G::NONE;
+    if (hit) {
+      bool done;
+      if constexpr (WS) done = shade_walk<COUNT, WMEM, HEAVY>(Q, ws, ps, winner, closest, r.o, r.d, r.tau, r.tau, sum, cn);
+      else done = shade<false, COUNT>(P, ps, winner, closest, r.o, r.d, r.tau, r.tau, cn); /* time = r.tau unless uniform (TRay) */
+      /* not scattered (a Metal scatter below the surface) or at the depth cap: the path is over; node NONE with the
+       * winner kept says so to the retire.  Otherwise the scattered ray (depth_left > 0) is set up */
+      setup = !(done || ps.depth_left == 0);
+      node = G::NONE;
+    }
+    n_seg += (uint32_t)__popcll(__ballot(hit));
+    stamp(2);
+  };
+
+  /* One pass of the instantiation that reads leaf lists: retire the paths that are over, claim work and start
+   * samples (their camera segments by the lists), shade every finished hit, set up the scattered rays, walk
+   * (DESIGN.md section 6.1).  The other instantiations have nothing between the walk loop and the claim that
+   * finishes a segment, so the order gains them nothing, and it cost Earth + Perlin's HEAVY packet kernel 2-3% in
+   * every form measured: they keep claim / start, one ray setup, walk, and one block that
+   * shades and retires, behind the walk loop. */
   for (;;) {
+    if constexpr (LISTS) {
+    /* retire: a sphere scene's path gathers radiance at its miss only, and most paths end at one, so the end of a
+     * path is known before shading.  Retiring here, ahead of the claim, lets the shading block below serve the
+     * walked and the listed hits in ONE execution (application.rs:448: samples of a chunk summed in order) */
+    const bool retire = path_over();
+    const bool miss = retire && node != G::NONE; /* a traced segment; `winner` is NONE */
+    bool chunk_done = false;
+    if (retire) {
+      if (miss) {
+        if constexpr (WS) sum = sum + mul_elem(ps.thr, P.background); /* shade_walk's miss: straight into the sum */
+        else ps.rad = ps.rad + mul_elem(ps.thr, P.background);        /* shade's miss */
+      }
+      if constexpr (!WS) sum = sum + ps.rad;
+      walking = false;
+      node = G::NONE;
+      if (++it.sample == it.sample_end) {
+        if (P.direct_out == 1) /* sqrt(sum / spp), alpha 1 (:451-456) */
+          P.out[*slot_lds] = make_float4(sqrtf(sum.x * scale), sqrtf(sum.y * scale), sqrtf(sum.z * scale), 1.0f);
+        else
+          P.partial[*slot_lds] = make_float4(sum.x, sum.y, sum.z, 0.0f);
+        chunk_done = true;
+        has_item = false;
+        sum = v3(0.0f, 0.0f, 0.0f);
+      }
+    }
+    n_seg += (uint32_t)__popcll(__ballot(miss)); /* the hits are counted where they are shaded */
+    n_samples += (uint32_t)__popcll(__ballot(retire));
+    n_pixels += (uint32_t)__popcll(__ballot(chunk_done && it.sample_end <= P.chunk));
+    }
     /* lanes without work claim it; lanes with work but no segment in flight start a sample */
     const bool had_item = has_item;
 #if HRT_CLAIM_BLOCKS
@@ -163,33 +241,18 @@ void render_basic_kernel(KParams P) {
       walking = true;
       setup = true;
     }
-    if (setup) { /* new samples and scattered rays share one pass through the ray setup (1/d, d.d) */
-#if HRT_RAY_REDERIVE_SPHERE
-      r.o = ps.ro;
-      r.d = ps.rd;
-      set_time(r, ps.rtime, P); /* a scattered ray keeps the sample's shutter time */
-#else
-      set_ray(r, ps.ro, ps.rd, ps.rtime, P);
-#endif
-      closest = inf;
-      winner = G::NONE;
-      node = ps.depth_left == 0 ? G::NONE : root; /* max_depth 0: black without a world.hit (:478-480) */
-      setup = false;
-    }
-#if HRT_RAY_REDERIVE_SPHERE
-    set_dir(r, r.o, r.d); /* every lane: dead across shading (kernel_common.h) */
-#endif
+    /* LISTS: the new samples' rays now (the list rounds need `r`), the scattered rays' behind the shading below.
+     * The other instantiations set up both there, in one execution per pass */
+    if constexpr (LISTS) setup_rays();
     /* The camera segment by its cell's leaf list: the lanes with a usable record (a
      * sample just started, depth left, no overflow, the ray not in NaN mode) take one ordinary node step on each
      * listed leaf, in leaf order, and the leaf's test where the step passes -- the steps and tests their walk
      * would make at its leaves, without the inner nodes.  They then hold a finished walk (node = end, nothing
      * pending).  The entry index is a constant in each round.
-     * A pass whose lists finished some segments is a SHORT pass: it skips the walk loop and shades those lanes at
-     * once, so their scattered rays are set up with the next pass and walk with the wave, instead of waiting out a
-     * walk loop they have no part in (which cost more than the lists saved: DESIGN.md section 10).  A short pass is
-     * never followed by another, so the lanes in the middle of a walk step at least every other pass; lanes listed in
-     * the pass after a short one wait for that pass's shading as every finished lane does. */
-    bool short_pass = false;
+     * The shading block follows at once, so a listed hit's scattered ray is set up in this pass and walks with the
+     * wave, instead of waiting out a walk loop it has no part in (which cost more than the lists saved: DESIGN.md
+     * section 10); a listed miss retires at the next pass's start (repeating the retire and the claim within the pass
+     * for such lanes, 2 or 4 trips, measured slower: section 10). */
     if constexpr (LISTS) {
       const bool listed = fresh && ps.depth_left != 0 && (rec.x & 0xFFFFu) != plist::PL_OVERFLOW && !nan_mode(r);
       if (__ballot(listed)) {
@@ -222,19 +285,18 @@ void render_basic_kernel(KParams P) {
             rec = P.prim_lists[(P.cells_xy & 0xFFFFu) * (P.cells_xy >> 16) + (it.pxy >> 19) * (P.cells_xy & 0xFFFFu) +
                                ((it.pxy & 0xFFFFu) >> 3)];
         }
-        short_pass = !short_prev;
       }
     }
-    short_prev = short_pass;
+    if constexpr (COUNT) cn.shade_slots++;
+    if constexpr (LISTS) shade_hits();
+    setup_rays(); /* LISTS: the scattered rays; the others: new samples and scattered rays in one execution */
     /* step the walks until enough lanes have finished (lanes not walking hold node >= end).  A lane
      * whose leaf box passed holds WALK_PEND in `node` and waits; the wave runs the sphere block
      * once `batch` lanes wait (or no lane can step), instead of for every lane that needs it. */
-    if constexpr (COUNT) cn.shade_slots++;
     stamp(0);
     const unsigned long long walkers = __ballot(walking);
     uint32_t iters = 0;
     bool stuck = false;
-    if (!short_pass) {
     if constexpr (PACKET) {
       /* the packet walk (render_general.hip PACKET): the wave at ONE position u, the lanes whose own position is u
        * active; a leaf's test runs at once for the lanes that pass its box, so each lane tests exactly its own
@@ -326,7 +388,6 @@ void render_basic_kernel(KParams P) {
       if (++iters > cap) { stuck = true; break; }
     }
     }
-    }
     if (stuck) { /* a walk that cannot end (corrupt scene data): report it, retire the wave */
       if (lane == 0) atomicOr(&P.stats[12], 1ull);
       exhausted = true;
@@ -336,41 +397,43 @@ void render_basic_kernel(KParams P) {
       pend = G::NONE;
     }
     stamp(1);
-    /* shade the finished segments (application.rs:483-494) */
-    const bool shading = walking && node >= end && !walk_pend<C16>(node) && (!SPEC || pend == G::NONE);
-    const bool traced = shading && node != G::NONE;
-    bool sample_done = false, chunk_done = false;
-    if (shading) {
-      bool done = true;
-      if (traced) {
-        if constexpr (WS) done = shade_walk<COUNT, WMEM, HEAVY>(Q, ws, ps, winner, closest, r.o, r.d, r.tau, r.tau, sum, cn);
-        else done = shade<false, COUNT>(P, ps, winner, closest, r.o, r.d, r.tau, r.tau, cn); /* time = r.tau unless uniform (TRay) */
-        done = done || ps.depth_left == 0;
-      }
-      if (done) {
-        /* application.rs:448: samples of a chunk summed in order */
-        walking = false;
-        node = G::NONE;
-        if constexpr (!WS) sum = sum + ps.rad; /* shade_walk added a miss's radiance already */
-        sample_done = true;
-        if (++it.sample == it.sample_end) {
-          if (P.direct_out == 1) /* sqrt(sum / spp), alpha 1 (:451-456) */
-            P.out[*slot_lds] = make_float4(sqrtf(sum.x * scale), sqrtf(sum.y * scale), sqrtf(sum.z * scale), 1.0f);
-          else
-            P.partial[*slot_lds] = make_float4(sum.x, sum.y, sum.z, 0.0f);
-          chunk_done = true;
-          has_item = false;
-          sum = v3(0.0f, 0.0f, 0.0f);
+    if constexpr (!LISTS) {
+      /* shade the finished segments (application.rs:483-494) */
+      const bool shading = finished();
+      const bool traced = shading && node != G::NONE;
+      bool sample_done = false, chunk_done = false;
+      if (shading) {
+        bool done = true;
+        if (traced) {
+          if constexpr (WS) done = shade_walk<COUNT, WMEM, HEAVY>(Q, ws, ps, winner, closest, r.o, r.d, r.tau, r.tau, sum, cn);
+          else done = shade<false, COUNT>(P, ps, winner, closest, r.o, r.d, r.tau, r.tau, cn); /* time = r.tau unless uniform (TRay) */
+          done = done || ps.depth_left == 0;
         }
-      } else {
-        setup = true; /* the scattered ray (depth_left > 0) is set up with the next pass's new samples */
-        node = G::NONE;
+        if (done) {
+          /* application.rs:448: samples of a chunk summed in order */
+          walking = false;
+          node = G::NONE;
+          if constexpr (!WS) sum = sum + ps.rad; /* shade_walk added a miss's radiance already */
+          sample_done = true;
+          if (++it.sample == it.sample_end) {
+            if (P.direct_out == 1) /* sqrt(sum / spp), alpha 1 (:451-456) */
+              P.out[*slot_lds] = make_float4(sqrtf(sum.x * scale), sqrtf(sum.y * scale), sqrtf(sum.z * scale), 1.0f);
+            else
+              P.partial[*slot_lds] = make_float4(sum.x, sum.y, sum.z, 0.0f);
+            chunk_done = true;
+            has_item = false;
+            sum = v3(0.0f, 0.0f, 0.0f);
+          }
+        } else {
+          setup = true; /* the scattered ray (depth_left > 0) is set up with the next pass's new samples */
+          node = G::NONE;
+        }
       }
+      n_seg += (uint32_t)__popcll(__ballot(traced));
+      n_samples += (uint32_t)__popcll(__ballot(sample_done));
+      n_pixels += (uint32_t)__popcll(__ballot(chunk_done && it.sample_end <= P.chunk));
+      stamp(2);
     }
-    n_seg += (uint32_t)__popcll(__ballot(traced));
-    n_samples += (uint32_t)__popcll(__ballot(sample_done));
-    n_pixels += (uint32_t)__popcll(__ballot(chunk_done && it.sample_end <= P.chunk));
-    stamp(2);
   }
   if (lane == 0) {
     atomicAdd(&P.stats[0], (unsigned long long)n_seg);
