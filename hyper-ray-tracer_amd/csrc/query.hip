@@ -13,6 +13,8 @@
  *                       forward (lane.h trace_ray), so every launch ends.
  *   camera_rays_kernel  one lane per pixel over the tile-block domain of features.hip; the lane writes its pixel's
  *                       samples' rays in index order.
+ *   camera_paths_kernel the same domain and rays for hrt_camera_paths, with each ray's starting path (scatter.h
+ *                       camera_path) written beside it.
  */
 #include <hip/hip_runtime.h>
 
@@ -23,6 +25,7 @@
 #include "kernel_common.h"
 #include "query.h"
 #include "render_host.h"
+#include "scatter.h"
 
 using namespace hrt;
 using namespace hrt::query;
@@ -84,6 +87,22 @@ __global__ __launch_bounds__(64) void camera_rays_kernel(KParams P, FeatureTile 
   if (lx >= T.w || ly >= T.h) return;
   const size_t at = ((size_t)T.off + (size_t)ly * T.w + lx) * P.spp; /* < 2^32: the entry point checks */
   for (uint32_t j = 0; j < P.spp; j++) store_ray(rays + at + j, camera_ray(P, T.x + lx, T.y + ly, j));
+}
+
+__global__ __launch_bounds__(64) void camera_paths_kernel(KParams P, FeatureTile one, const FeatureTile* __restrict__ tiles,
+                                                          uint32_t n_tiles, uint32_t log_bw, hrt_ray* __restrict__ rays,
+                                                          hrt_path* __restrict__ paths) {
+  const FeatureTile T = n_tiles == 1u ? one : tile_of_block(tiles, n_tiles, blockIdx.x);
+  const uint32_t bw = 1u << log_bw, bh = 64u >> log_bw;
+  const uint32_t nbx = (T.w + bw - 1) / bw, k = blockIdx.x - T.blk0;
+  const uint32_t lx = (k % nbx) * bw + (threadIdx.x & (bw - 1)), ly = (k / nbx) * bh + (threadIdx.x >> log_bw);
+  if (lx >= T.w || ly >= T.h) return;
+  const size_t at = ((size_t)T.off + (size_t)ly * T.w + lx) * P.spp; /* < 2^32: the entry point checks */
+  for (uint32_t j = 0; j < P.spp; j++) {
+    const scatterq::CameraPath c = scatterq::camera_path(P, T.x + lx, T.y + ly, j);
+    store_ray(rays + at + j, c.ray);
+    scatterq::store_path(paths + at + j, c.path);
+  }
 }
 
 template <int CULL, bool FULL, bool MEDIA, bool LDS>
@@ -199,6 +218,41 @@ void check_camera_args(const hrt_scene* s, const hrt_camera* cam, const hrt_rend
   if (!s->committed || !s->d_blob) throw HipError{HRT_ERR_STATE, "scene not committed"};
 }
 
+/* the launch of hrt_camera_rays (d_paths null) and hrt_camera_paths, after the argument checks */
+void camera_launch(hrt_scene* s, const hrt_camera* cam, const hrt_render_params* p, const hrt_tile* tiles, uint32_t n_tiles,
+                   hrt_ray* d_rays, hrt_path* d_paths, void* stream_) {
+  const uint32_t log_bw = features::block_log_w();
+  uint64_t n_pixels = 0;
+  uint32_t n_blocks = 0;
+  const std::vector<FeatureTile> ft = ray_tiles(p, tiles, n_tiles, log_bw, n_pixels, n_blocks);
+  hipStream_t stream = (hipStream_t)stream_;
+  DeviceGuard dg(s->device);
+  KParams kp;
+  memset(&kp, 0, sizeof(kp));
+  set_camera_params(kp, cam, p);
+  FeatureTile* d_tiles = nullptr;
+  if (n_tiles > 1) { /* the table goes to the device in stream order; the call then waits, so `ft` outlives the copy */
+    hip_check(hipMallocAsync((void**)&d_tiles, ft.size() * sizeof(FeatureTile), stream), "hipMallocAsync(ray tiles)");
+    try {
+      hip_check(hipMemcpyAsync(d_tiles, ft.data(), ft.size() * sizeof(FeatureTile), hipMemcpyHostToDevice, stream),
+                "hipMemcpyAsync(ray tiles)");
+    } catch (...) {
+      (void)hipFreeAsync(d_tiles, stream);
+      throw;
+    }
+  }
+  if (d_paths)
+    hipLaunchKernelGGL(camera_paths_kernel, dim3(n_blocks), dim3(64), 0, stream, kp, ft[0], d_tiles, n_tiles, log_bw, d_rays, d_paths);
+  else
+    hipLaunchKernelGGL(camera_rays_kernel, dim3(n_blocks), dim3(64), 0, stream, kp, ft[0], d_tiles, n_tiles, log_bw, d_rays);
+  const hipError_t launched = hipGetLastError();
+  if (d_tiles) {
+    (void)hipFreeAsync(d_tiles, stream);
+    hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize(ray tiles)");
+  }
+  hip_check(launched, d_paths ? "camera_paths_kernel launch" : "camera_rays_kernel launch");
+}
+
 }  // namespace
 
 extern "C" {
@@ -242,33 +296,7 @@ hrt_status hrt_camera_rays(hrt_scene* s, const hrt_camera* cam, const hrt_render
                            hrt_ray* d_rays, void* stream_) {
   return hguard([&] {
     check_camera_args(s, cam, p, tiles, n_tiles, d_rays, true, "hrt_camera_rays");
-    const uint32_t log_bw = features::block_log_w();
-    uint64_t n_pixels = 0;
-    uint32_t n_blocks = 0;
-    const std::vector<FeatureTile> ft = ray_tiles(p, tiles, n_tiles, log_bw, n_pixels, n_blocks);
-    hipStream_t stream = (hipStream_t)stream_;
-    DeviceGuard dg(s->device);
-    KParams kp;
-    memset(&kp, 0, sizeof(kp));
-    set_camera_params(kp, cam, p);
-    FeatureTile* d_tiles = nullptr;
-    if (n_tiles > 1) { /* the table goes to the device in stream order; the call then waits, so `ft` outlives the copy */
-      hip_check(hipMallocAsync((void**)&d_tiles, ft.size() * sizeof(FeatureTile), stream), "hipMallocAsync(ray tiles)");
-      try {
-        hip_check(hipMemcpyAsync(d_tiles, ft.data(), ft.size() * sizeof(FeatureTile), hipMemcpyHostToDevice, stream),
-                  "hipMemcpyAsync(ray tiles)");
-      } catch (...) {
-        (void)hipFreeAsync(d_tiles, stream);
-        throw;
-      }
-    }
-    hipLaunchKernelGGL(camera_rays_kernel, dim3(n_blocks), dim3(64), 0, stream, kp, ft[0], d_tiles, n_tiles, log_bw, d_rays);
-    const hipError_t launched = hipGetLastError();
-    if (d_tiles) {
-      (void)hipFreeAsync(d_tiles, stream);
-      hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize(ray tiles)");
-    }
-    hip_check(launched, "camera_rays_kernel launch");
+    camera_launch(s, cam, p, tiles, n_tiles, d_rays, nullptr, stream_);
   });
 }
 
@@ -288,6 +316,38 @@ hrt_status hrt_camera_rays_host(hrt_scene* s, const hrt_camera* cam, const hrt_r
     const hrt_status r = hrt_camera_rays(s, cam, p, tiles, n_tiles, d_rays.p, nullptr);
     if (r != HRT_OK) throw HipError{r, hrt_last_error()};
     hip_check(hipMemcpy(rays, d_rays.p, bytes, hipMemcpyDeviceToHost), "hipMemcpy(rays)");
+  });
+}
+
+hrt_status hrt_camera_paths(hrt_scene* s, const hrt_camera* cam, const hrt_render_params* p, const hrt_tile* tiles, uint32_t n_tiles,
+                            hrt_ray* d_rays, hrt_path* d_paths, void* stream_) {
+  return hguard([&] {
+    if (!d_paths) throw HipError{HRT_ERR_INVALID_ARG, "hrt_camera_paths: null argument"};
+    if (!aligned16(d_paths)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_camera_paths: the records must be 16-byte aligned"};
+    check_camera_args(s, cam, p, tiles, n_tiles, d_rays, true, "hrt_camera_paths");
+    camera_launch(s, cam, p, tiles, n_tiles, d_rays, d_paths, stream_);
+  });
+}
+
+hrt_status hrt_camera_paths_host(hrt_scene* s, const hrt_camera* cam, const hrt_render_params* p, const hrt_tile* tiles,
+                                 uint32_t n_tiles, hrt_ray* rays, hrt_path* paths) {
+  uint64_t n_pixels = 0;
+  hrt_status st = hguard([&] {
+    if (!paths) throw HipError{HRT_ERR_INVALID_ARG, "hrt_camera_paths_host: null argument"};
+    check_camera_args(s, cam, p, tiles, n_tiles, rays, false, "hrt_camera_paths_host");
+    uint32_t n_blocks = 0;
+    (void)ray_tiles(p, tiles, n_tiles, features::block_log_w(), n_pixels, n_blocks);
+  });
+  if (st != HRT_OK) return st;
+  return hguard([&] {
+    DeviceGuard dg(s->device);
+    const size_t n = (size_t)n_pixels * p->samples;
+    DevBuf<hrt_ray> d_rays(n * sizeof(hrt_ray));
+    DevBuf<hrt_path> d_paths(n * sizeof(hrt_path));
+    const hrt_status r = hrt_camera_paths(s, cam, p, tiles, n_tiles, d_rays.p, d_paths.p, nullptr);
+    if (r != HRT_OK) throw HipError{r, hrt_last_error()};
+    hip_check(hipMemcpy(rays, d_rays.p, n * sizeof(hrt_ray), hipMemcpyDeviceToHost), "hipMemcpy(rays)");
+    hip_check(hipMemcpy(paths, d_paths.p, n * sizeof(hrt_path), hipMemcpyDeviceToHost), "hipMemcpy(paths)");
   });
 }
 

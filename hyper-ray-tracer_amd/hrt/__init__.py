@@ -193,6 +193,18 @@ HIT_HIT, HIT_FRONT, HIT_MEDIUM, HIT_INVALID = 1, 2, 4, 8
 QUERY_SKIP_MEDIA, QUERY_NO_LDS, QUERY_REFERENCE_CULL = 1, 2, 4
 
 
+class ScatterParams(ctypes.Structure):
+    """hrt_scatter_params (24 bytes): flags (none defined), the background a miss gathers, two reserved words."""
+    _fields_ = [("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("background", ctypes.c_float * 3),
+                ("reserved2", ctypes.c_uint32)]
+
+
+# hrt_path (48 bytes): a caller-held path between hrt_scene_intersect and hrt_scene_scatter
+PATH_DTYPE = np.dtype([("rng", np.uint32, 4), ("throughput", np.float32, 3), ("depth_left", np.uint32),
+                       ("radiance", np.float32, 3), ("flags", np.uint32)])
+PATH_DONE, PATH_MISSED, PATH_ABSORBED, PATH_DEPTH, PATH_INVALID = 1, 2, 4, 8, 16
+
+
 # Diagnostics an older build may lack; only tolerated when HRT_LIB points at another build (A/B runs)
 OPTIONAL = {"hrt_abi_version", "hrt_last_launch", "hrt_debug_box_test", "hrt_scene_set_options", "hrt_scene_get_options",
             "hrt_debug_sample_chunks", "hrt_scene_set_view",
@@ -207,7 +219,8 @@ OPTIONAL = {"hrt_abi_version", "hrt_last_launch", "hrt_debug_box_test", "hrt_sce
             "hrt_accum_snapshot", "hrt_accum_restore", "hrt_accum_snapshot_info", "hrt_accum_merge_tiles",
             "hrt_accum_resolve_guided_ex", "hrt_accum_resolve_guided_ex_host", "hrt_debug_guided_ex",
             "hrt_accum_noise_filtered", "hrt_debug_noise_filtered",
-            "hrt_scene_intersect", "hrt_scene_intersect_host", "hrt_camera_rays", "hrt_camera_rays_host"}
+            "hrt_scene_intersect", "hrt_scene_intersect_host", "hrt_camera_rays", "hrt_camera_rays_host",
+            "hrt_scene_scatter", "hrt_scene_scatter_host", "hrt_camera_paths", "hrt_camera_paths_host"}
 HRT_LIB_OVERRIDE = bool(os.environ.get("HRT_LIB"))
 
 # Every entry point of include/hrt/hrt.h (tests/test_abi.py checks the header against this list).
@@ -234,6 +247,7 @@ EXPORTS = [
     "hrt_accum_resolve_guided_ex", "hrt_accum_resolve_guided_ex_host", "hrt_debug_guided_ex",
     "hrt_accum_noise_filtered", "hrt_debug_noise_filtered",
     "hrt_scene_intersect", "hrt_scene_intersect_host", "hrt_camera_rays", "hrt_camera_rays_host",
+    "hrt_scene_scatter", "hrt_scene_scatter_host", "hrt_camera_paths", "hrt_camera_paths_host",
 ]
 
 ABI_VERSION = 6  # include/hrt/hrt.h HRT_ABI_VERSION: the struct layouts below
@@ -357,6 +371,10 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "hrt_scene_intersect_host": (S, [vp, ctypes.POINTER(QueryParams), vp, u64, vp]),
         "hrt_camera_rays": (S, [vp, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams), vp, u32, vp, vp]),
         "hrt_camera_rays_host": (S, [vp, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams), vp, u32, vp]),
+        "hrt_scene_scatter": (S, [vp, ctypes.POINTER(ScatterParams), vp, vp, vp, u64, vp]),
+        "hrt_scene_scatter_host": (S, [vp, ctypes.POINTER(ScatterParams), vp, vp, vp, u64]),
+        "hrt_camera_paths": (S, [vp, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams), vp, u32, vp, vp, vp]),
+        "hrt_camera_paths_host": (S, [vp, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams), vp, u32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         if name in OPTIONAL and HRT_LIB_OVERRIDE and not hasattr(L, name):
@@ -551,6 +569,32 @@ class Scene:
         _check(load().hrt_scene_intersect(self.h, ctypes.byref(q), rays.data_ptr(), n, hits.data_ptr(), stream or None))
         return hits
 
+    def scatter(self, rays, hits, paths, background, stream: int = 0):
+        """One scatter step of every path that is not DONE (hrt_scene_scatter): the miss's background or the hit's
+        emission, scatter and texture, drawn from the path's own stream.  numpy arrays (RAY_DTYPE, HIT_DTYPE, PATH_DTYPE)
+        go through the host variant and NEW (rays, paths) arrays come back; contiguous CUDA tensors of 48-byte records go
+        through the device variant on `stream`, which updates rays and paths IN PLACE and returns them."""
+        sp = scatter_params(background)
+        if isinstance(rays, np.ndarray):
+            rays, paths = np.array(rays, RAY_DTYPE, order="C"), np.array(paths, PATH_DTYPE, order="C")  # copies
+            hits = np.ascontiguousarray(hits, HIT_DTYPE)
+            if not (rays.shape == hits.shape == paths.shape):
+                raise ValueError("rays, hits and paths: arrays of one shape")
+            _check(load().hrt_scene_scatter_host(self.h, ctypes.byref(sp), rays.ctypes.data, hits.ctypes.data, paths.ctypes.data,
+                                                 rays.size))
+            return rays, paths
+        import torch
+
+        def records(t):
+            ok = isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.numel() * t.element_size() % 48 == 0
+            return t.numel() * t.element_size() // 48 if ok else -1
+
+        n = records(rays)
+        if n < 0 or records(hits) != n or records(paths) != n:
+            raise ValueError("rays, hits, paths: numpy record arrays, or contiguous CUDA tensors of n 48-byte records each")
+        _check(load().hrt_scene_scatter(self.h, ctypes.byref(sp), rays.data_ptr(), hits.data_ptr(), paths.data_ptr(), n, stream or None))
+        return rays, paths
+
     def scene_info(self) -> SceneInfo:
         si = SceneInfo()
         _check(load().hrt_scene_get_info(self.h, ctypes.byref(si)))
@@ -648,6 +692,55 @@ def camera_rays(scene: "Scene", cam: Camera, p: RenderParams, tiles=None, device
     rays = torch.empty((n, 12), dtype=torch.float32, device="cuda")
     _check(load().hrt_camera_rays(scene.h, ctypes.byref(cam), ctypes.byref(p), arr, len(tiles), rays.data_ptr(), stream or None))
     return rays
+
+
+def scatter_params(background, flags: int = 0) -> ScatterParams:
+    """hrt_scatter_params: the background a miss gathers (a render's p.background); no flag is defined yet."""
+    return ScatterParams(flags, 0, _F3(*[float(x) for x in background]), 0)
+
+
+def camera_paths(scene: "Scene", cam: Camera, p: RenderParams, tiles=None, device: bool = False, stream: int = 0):
+    """hrt.camera_rays' rays and, for each, the path a render's sample starts with (hrt_camera_paths): (rays, paths) as
+    RAY_DTYPE and PATH_DTYPE arrays, or with device=True as two (n, 12) float32 CUDA tensors (view the paths as int32 for
+    rng, depth_left and flags: words 0..3, 7 and 11)."""
+    tiles = [(0, 0, p.width, p.height)] if tiles is None else list(tiles)
+    arr = (Tile * len(tiles))(*[Tile(*t) for t in tiles])
+    n = sum(t[2] * t[3] for t in tiles) * p.samples
+    if not device:
+        rays, paths = np.empty(n, RAY_DTYPE), np.empty(n, PATH_DTYPE)
+        _check(load().hrt_camera_paths_host(scene.h, ctypes.byref(cam), ctypes.byref(p), arr, len(tiles), rays.ctypes.data,
+                                            paths.ctypes.data))
+        return rays, paths
+    import torch
+
+    rays = torch.empty((n, 12), dtype=torch.float32, device="cuda")
+    paths = torch.empty((n, 12), dtype=torch.float32, device="cuda")
+    _check(load().hrt_camera_paths(scene.h, ctypes.byref(cam), ctypes.byref(p), arr, len(tiles), rays.data_ptr(), paths.data_ptr(),
+                                   stream or None))
+    return rays, paths
+
+
+def trace_paths(scene: "Scene", cam: Camera, p: RenderParams, tiles=None, device: bool = False):
+    """Your own integrator in a dozen lines: the render's paths through the query calls, on the device.  Camera paths,
+    then intersect and scatter in turn until every path is DONE (at most p.max_depth rounds).  Returns the per-sample
+    radiance (n, 3) float32, path (packed pixel) * p.samples + k, bit for bit what hrt.render gathers for sample
+    p.sample_offset + k of that pixel, and the number of rays traced, which is the render's RenderStats.segments.
+    device=True: the finished paths stay on the device, an (n, 12) float32 CUDA tensor of hrt_path records (radiance:
+    columns 8..10), instead of the downloaded radiance."""
+    import torch
+
+    rays, paths = camera_paths(scene, cam, p, tiles, device=True)
+    path_flags = paths.view(torch.int32)[:, 11]
+    hits = torch.empty_like(rays)
+    hit_flags = hits.view(torch.int32)[:, 3]
+    n_rays = 0
+    for _ in range(p.max_depth):
+        if not bool((path_flags & PATH_DONE == 0).any()):
+            break
+        scene.intersect(rays, seed=p.seed, shutter=(cam.time0, cam.time1), out=hits)
+        n_rays += int((hit_flags & HIT_INVALID == 0).sum())  # a finished path's ray is invalid and was not traced
+        scene.scatter(rays, hits, paths, tuple(p.background))
+    return (paths if device else paths[:, 8:11].cpu().numpy()), n_rays
 
 
 def tile_grid(width: int, height: int, tile_size: int = 80, rank: int = 0, world: int = 1) -> List[Tuple[int, int, int, int]]:

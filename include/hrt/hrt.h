@@ -779,6 +779,89 @@ hrt_status hrt_camera_rays(hrt_scene* s, const hrt_camera* cam, const hrt_render
 hrt_status hrt_camera_rays_host(hrt_scene* s, const hrt_camera* cam, const hrt_render_params* p, const hrt_tile* tiles,
                                 uint32_t n_tiles, hrt_ray* rays);
 
+/* ---- scatter queries: caller-held paths stepped through the scene's materials ----
+ * hrt_scene_intersect is the world.hit of one ray_color step; hrt_scene_scatter is the rest of that step (lane.h shade:
+ * background on a miss, else emission, the material's scatter and its texture), for paths the caller keeps in device
+ * memory between the calls; hrt_camera_paths starts paths exactly as a render starts its samples.  A custom integrator,
+ * per-bounce AOVs, light-path statistics (examples/render_integrator.c; hrt.trace_paths in the Python binding).
+ *
+ * A PATH is the 48-byte record below: the xoshiro128** state of its random stream, its throughput, its radiance so far,
+ * the segments it may still trace and HRT_PATH_* flags.  Path i belongs to ray i and hit i of the same batch.
+ *
+ * hrt_scene_scatter, for path i, in this order (csrc/scatter.h scatter_step, -ffp-contract=off, all in f32):
+ *   1. DONE on entry: nothing of ray i or path i is written.
+ *   2. An invalid hit - HRT_HIT_INVALID set, flag bits outside the four HRT_HIT_* ones, HRT_HIT_HIT with a material
+ *      that is not below the scene's material count, or other bits without HRT_HIT_HIT (no record hrt_scene_intersect
+ *      writes): path flags |= INVALID | DONE and nothing else of the path changes.
+ *      The material id is the one field of a caller's record that indexes a table; it is checked before any read.
+ *      Everything else in a hit is used as a number.  A path whose four rng words are all 0 is refused the same way:
+ *      that is no xoshiro state (it never leaves 0, and the rejection loops of the draws would never end), and
+ *      hrt_camera_paths never writes it.  A path that is not DONE with depth_left == 0 (none this library writes) takes
+ *      the render's depth cap: flags |= DEPTH | DONE, nothing else changes.
+ *   3. A miss (flags 0): radiance = radiance + throughput * background (componentwise; shade()'s expression and order),
+ *      flags |= MISSED | DONE.
+ *   4. A hit: the record is the step's HitRecord - point, normal, front bit, u, v and material as given, the incoming
+ *      direction ray.direction.  The step is lane.h scatter<true> with the scene's material and its texture: it draws
+ *      from rng exactly as a render does (random_in_unit_sphere for a Lambertian, a Metal and an Isotropic, one f32 for
+ *      a Dielectric, nothing for a DiffuseLight).  radiance += throughput * emitted.  Not scattered (a light, or a
+ *      metal ray below the surface): flags |= ABSORBED | DONE.  Scattered: throughput *= attenuation, depth_left -= 1,
+ *      ray origin = the hit's point, direction = the scattered direction, segment += 1, t_max = +inf; t_min, time,
+ *      pixel and sample are kept; if depth_left is now 0, flags |= DEPTH | DONE (the render's next segment would
+ *      return black without a world.hit).
+ *   5. A path that becomes DONE in this call has its ray written with t_max = t_min, which hrt_scene_intersect answers
+ *      as an invalid ray without a walk: a caller may keep calling both functions on the whole batch, uncompacted.
+ *   What a result depends on.  Ray i and path i after the call are a function of ray i, hit i and path i before it,
+ *   the params and the committed scene ALONE: never of n, of the position in the batch, of the other records, of where
+ *   the kernel keeps the scene's Perlin tables (HRT_SCATTER_PERLIN_LDS=0, an A/B knob) or of the device.  Records [n ..)
+ *   are never written.
+ *
+ * THE BIT CONTRACT with the render.  For a committed scene, a camera and render params p whose flags select no
+ * approximate culling: hrt_camera_paths once, then hrt_scene_intersect (seed = p->seed, [time0, time1] = the camera's
+ * shutter) and hrt_scene_scatter (background = p->background) in turn until every path is DONE, which takes at most
+ * p->max_depth rounds.  Then path (pixel, k)'s radiance is, bit for bit, the radiance a render gives sample
+ * p->sample_offset + k of that pixel; sqrtf(radiance * 1.0f) is hrt_render's pixel for samples = 1 and that sample
+ * offset; and the number of valid, not-DONE rays handed to hrt_scene_intersect over all rounds is the render's ray
+ * count (hrt_render_stats.segments).  Excluded: a path that meets a non-finite hit (a rect's t = NaN).  The render
+ * walks on from a NaN point up to the depth cap; here the next hrt_scene_intersect refuses the ray and the path ends
+ * INVALID.  Sphere scenes cannot produce such a hit.
+ *
+ * d_rays, d_hits and d_paths are device memory, n records of 48 bytes each, 16-byte aligned, none overlapping; rays and
+ * paths are read and written in place, hits are read only.  The work is asynchronous on `stream`.
+ * Errors, each changing nothing and answered before any device call: HRT_ERR_INVALID_ARG for a null scene, params or
+ * buffer (n == 0 is HRT_OK whatever the buffers, and launches nothing), a misaligned buffer, unknown flags, a non-zero
+ * reserved word, a non-finite background component, n >= 2^32; HRT_ERR_STATE for an uncommitted scene. */
+typedef struct hrt_path hrt_path;
+struct hrt_path { /* 48 bytes */
+  uint32_t rng[4];     /* the path's xoshiro128** state (hd_math.h Rng s0 .. s3) */
+  float throughput[3]; /* the product of the attenuations so far */
+  uint32_t depth_left; /* segments the path may still trace */
+  float radiance[3];   /* emitted and background light gathered so far */
+  uint32_t flags;      /* HRT_PATH_* */
+};
+enum { HRT_PATH_DONE = 1, HRT_PATH_MISSED = 2, HRT_PATH_ABSORBED = 4, HRT_PATH_DEPTH = 8, HRT_PATH_INVALID = 16 };
+typedef struct hrt_scatter_params hrt_scatter_params;
+struct hrt_scatter_params { /* 24 bytes */
+  uint32_t flags;      /* 0: no flag is defined yet */
+  uint32_t reserved;   /* 0 */
+  float background[3]; /* what a miss gathers; finite */
+  uint32_t reserved2;  /* 0 */
+};
+hrt_status hrt_scene_scatter(hrt_scene* s, const hrt_scatter_params* sp, hrt_ray* d_rays, const hrt_hit* d_hits, hrt_path* d_paths,
+                             uint64_t n, void* stream);
+/* ... with rays, hits and paths in HOST memory: copies in, runs the device path on the scene's device, copies rays and
+ * paths out; synchronous */
+hrt_status hrt_scene_scatter_host(hrt_scene* s, const hrt_scatter_params* sp, hrt_ray* rays, const hrt_hit* hits, hrt_path* paths,
+                                  uint64_t n);
+/* hrt_camera_rays' rays, word for word (the same packing, checks and 2^32 limit), and for each ray the path a render's
+ * sample starts with (lane.h start_sample): rng after the jitter, lens and shutter draws - which only this call can
+ * supply - throughput (1, 1, 1), radiance +0, depth_left = p->max_depth, flags 0.  With p->max_depth == 0 every path
+ * starts DONE | DEPTH and its ray carries t_max = t_min (rule 5 above).  d_paths: as d_rays, one path per ray. */
+hrt_status hrt_camera_paths(hrt_scene* s, const hrt_camera* cam, const hrt_render_params* p, const hrt_tile* tiles,
+                            uint32_t n_tiles, hrt_ray* d_rays, hrt_path* d_paths, void* stream);
+/* ... into HOST memory; synchronous */
+hrt_status hrt_camera_paths_host(hrt_scene* s, const hrt_camera* cam, const hrt_render_params* p, const hrt_tile* tiles,
+                                 uint32_t n_tiles, hrt_ray* rays, hrt_path* paths);
+
 /* ---- diagnostics ---- */
 /* Device occupancy / layout facts of the committed scene (for DESIGN/bench). */
 typedef struct hrt_scene_info {
