@@ -21,8 +21,7 @@
 #include <cstring>
 
 #include "kernel_common.h"
-#include "render_host.h"
-#include "scatter.h"
+#include "query_host.h"
 
 using namespace hrt;
 using namespace hrt::scatterq;
@@ -53,25 +52,6 @@ __global__ __launch_bounds__(SCATTER_THREADS) void scatter_staged_kernel(KParams
 }
 
 constexpr size_t SCATTER_PERLIN_MAX_BYTES = 4 * sizeof(G::Perlin); /* 48 KB: three workgroups a CU keep their tables */
-
-/* what scatter_step reads of the committed scene (scatter.h) */
-KParams scene_scatter_params(const hrt_scene* s, const hrt_scatter_params* sp) {
-  KParams kp;
-  memset(&kp, 0, sizeof(kp));
-  const uint8_t* base = (const uint8_t*)s->d_blob;
-  kp.mats = (const G::Mat*)(base + s->off_mats);
-  kp.texs = (const G::Tex*)(base + s->off_texs);
-  kp.perlin = (const G::Perlin*)(base + s->off_perlin);
-  kp.images = base + s->off_images;
-  kp.n_mats = (uint32_t)s->g_mats.size();
-  kp.n_texs = (uint32_t)s->g_texs.size();
-  kp.n_perlin = (uint32_t)s->perlin.size();
-  kp.perlin_lds = 0u;
-  kp.background = v3(sp->background[0], sp->background[1], sp->background[2]);
-  return kp;
-}
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 /* the argument checks of both entry points, before any device call */
 void check_scatter_args(const hrt_scene* s, const hrt_scatter_params* sp, const void* rays, const void* hits, const void* paths,

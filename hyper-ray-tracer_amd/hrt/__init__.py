@@ -205,6 +205,22 @@ PATH_DTYPE = np.dtype([("rng", np.uint32, 4), ("throughput", np.float32, 3), ("d
 PATH_DONE, PATH_MISSED, PATH_ABSORBED, PATH_DEPTH, PATH_INVALID = 1, 2, 4, 8, 16
 
 
+class StepParams(ctypes.Structure):
+    """hrt_step_params (40 bytes): STEP_* flags (the QUERY_* ones), the rounds a live path makes inside the call, the
+    interval the rays' times lie in, the seed of the media's draws, the background a miss gathers."""
+    _fields_ = [("flags", ctypes.c_uint32), ("steps", ctypes.c_uint32), ("time0", ctypes.c_float), ("time1", ctypes.c_float),
+                ("seed", ctypes.c_uint64), ("background", ctypes.c_float * 3), ("reserved", ctypes.c_uint32)]
+
+
+class PathList(ctypes.Structure):
+    """hrt_path_list (24 bytes): a host struct of device pointers, `capacity` u32 indices and one u32 count."""
+    _fields_ = [("d_index", ctypes.c_void_p), ("d_count", ctypes.c_void_p), ("capacity", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+STEP_SKIP_MEDIA, STEP_NO_LDS, STEP_REFERENCE_CULL = 1, 2, 4
+
+
 # Diagnostics an older build may lack; only tolerated when HRT_LIB points at another build (A/B runs)
 OPTIONAL = {"hrt_abi_version", "hrt_last_launch", "hrt_debug_box_test", "hrt_scene_set_options", "hrt_scene_get_options",
             "hrt_debug_sample_chunks", "hrt_scene_set_view",
@@ -220,7 +236,8 @@ OPTIONAL = {"hrt_abi_version", "hrt_last_launch", "hrt_debug_box_test", "hrt_sce
             "hrt_accum_resolve_guided_ex", "hrt_accum_resolve_guided_ex_host", "hrt_debug_guided_ex",
             "hrt_accum_noise_filtered", "hrt_debug_noise_filtered",
             "hrt_scene_intersect", "hrt_scene_intersect_host", "hrt_camera_rays", "hrt_camera_rays_host",
-            "hrt_scene_scatter", "hrt_scene_scatter_host", "hrt_camera_paths", "hrt_camera_paths_host"}
+            "hrt_scene_scatter", "hrt_scene_scatter_host", "hrt_camera_paths", "hrt_camera_paths_host",
+            "hrt_scene_step", "hrt_scene_step_host"}
 HRT_LIB_OVERRIDE = bool(os.environ.get("HRT_LIB"))
 
 # Every entry point of include/hrt/hrt.h (tests/test_abi.py checks the header against this list).
@@ -248,6 +265,7 @@ EXPORTS = [
     "hrt_accum_noise_filtered", "hrt_debug_noise_filtered",
     "hrt_scene_intersect", "hrt_scene_intersect_host", "hrt_camera_rays", "hrt_camera_rays_host",
     "hrt_scene_scatter", "hrt_scene_scatter_host", "hrt_camera_paths", "hrt_camera_paths_host",
+    "hrt_scene_step", "hrt_scene_step_host",
 ]
 
 ABI_VERSION = 6  # include/hrt/hrt.h HRT_ABI_VERSION: the struct layouts below
@@ -375,6 +393,8 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "hrt_scene_scatter_host": (S, [vp, ctypes.POINTER(ScatterParams), vp, vp, vp, u64]),
         "hrt_camera_paths": (S, [vp, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams), vp, u32, vp, vp, vp]),
         "hrt_camera_paths_host": (S, [vp, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams), vp, u32, vp, vp]),
+        "hrt_scene_step": (S, [vp, ctypes.POINTER(StepParams), vp, vp, u64, vp, ctypes.POINTER(PathList), ctypes.POINTER(PathList), vp, vp]),
+        "hrt_scene_step_host": (S, [vp, ctypes.POINTER(StepParams), vp, vp, u64, vp, ctypes.POINTER(u64)]),
     }
     for name, (res, args) in sig.items():
         if name in OPTIONAL and HRT_LIB_OVERRIDE and not hasattr(L, name):
@@ -595,6 +615,61 @@ class Scene:
         _check(load().hrt_scene_scatter(self.h, ctypes.byref(sp), rays.data_ptr(), hits.data_ptr(), paths.data_ptr(), n, stream or None))
         return rays, paths
 
+    def step(self, rays, paths, *, steps: int = 1, seed: int = 0, shutter=(0.0, 1.0), background=(0.0, 0.0, 0.0), flags: int = 0,
+             hits=None, live=None, live_out=None, n_rays=None, stream: int = 0):
+        """`steps` rounds of intersect and scatter for every path of the domain that is not DONE, fused, with no hit
+        records in between (hrt_scene_step).  numpy arrays (RAY_DTYPE, PATH_DTYPE) go through the host variant and NEW
+        (rays, paths) arrays come back; `hits` (a HIT_DTYPE array) and `n_rays` (a one-element uint64 / int64 array, added
+        to) are then filled in place.  Contiguous CUDA tensors of 48-byte records go through the device variant on
+        `stream`, which updates rays and paths IN PLACE and returns them; hits: a tensor of n hit records to fill (the last
+        intersect's hit of each stepped path); live: the domain as an (index tensor int32, count tensor int32[1]) pair
+        (default: every path); live_out: such a pair that takes the paths still live, the next call's `live`; n_rays: an
+        int64 tensor of one element the call adds the rays it walked to."""
+        sp = step_params(steps, seed, shutter, background, flags)
+        L = load()
+        if isinstance(rays, np.ndarray):
+            if live is not None or live_out is not None:
+                raise ValueError("live lists are device memory: use CUDA tensors")
+            rays, paths = np.array(rays, RAY_DTYPE, order="C"), np.array(paths, PATH_DTYPE, order="C")  # copies
+            if rays.shape != paths.shape:
+                raise ValueError("rays and paths: arrays of one shape")
+            if hits is not None and (hits.dtype != HIT_DTYPE or hits.shape != rays.shape or not hits.flags.c_contiguous):
+                raise ValueError("hits: a contiguous HIT_DTYPE array of the rays' shape")
+            count = ctypes.c_uint64(0)
+            _check(L.hrt_scene_step_host(self.h, ctypes.byref(sp), rays.ctypes.data, paths.ctypes.data, rays.size,
+                                         None if hits is None else hits.ctypes.data, None if n_rays is None else ctypes.byref(count)))
+            if n_rays is not None:
+                n_rays[0] += count.value
+            return rays, paths
+        import torch
+
+        def records(t):
+            ok = isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.numel() * t.element_size() % 48 == 0
+            return t.numel() * t.element_size() // 48 if ok else -1
+
+        def path_list(pair, what):
+            if pair is None:
+                return None
+            index, count = pair
+            for t in (index, count):
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == torch.int32):
+                    raise ValueError(what + ": an (index, count) pair of contiguous int32 CUDA tensors")
+            if count.numel() != 1:
+                raise ValueError(what + ": the count is one int32")
+            return PathList(index.data_ptr(), count.data_ptr(), index.numel(), 0)
+
+        n = records(rays)
+        if n < 0 or records(paths) != n or (hits is not None and records(hits) != n):
+            raise ValueError("rays, paths (and hits): numpy record arrays, or contiguous CUDA tensors of n 48-byte records each")
+        if n_rays is not None and not (isinstance(n_rays, torch.Tensor) and n_rays.is_cuda and n_rays.dtype == torch.int64 and
+                                       n_rays.numel() == 1):
+            raise ValueError("n_rays: an int64 CUDA tensor of one element")
+        lin, lout = path_list(live, "live"), path_list(live_out, "live_out")
+        _check(L.hrt_scene_step(self.h, ctypes.byref(sp), rays.data_ptr(), paths.data_ptr(), n, None if hits is None else hits.data_ptr(),
+                                None if lin is None else ctypes.byref(lin), None if lout is None else ctypes.byref(lout),
+                                None if n_rays is None else n_rays.data_ptr(), stream or None))
+        return rays, paths
+
     def scene_info(self) -> SceneInfo:
         si = SceneInfo()
         _check(load().hrt_scene_get_info(self.h, ctypes.byref(si)))
@@ -741,6 +816,35 @@ def trace_paths(scene: "Scene", cam: Camera, p: RenderParams, tiles=None, device
         n_rays += int((hit_flags & HIT_INVALID == 0).sum())  # a finished path's ray is invalid and was not traced
         scene.scatter(rays, hits, paths, tuple(p.background))
     return (paths if device else paths[:, 8:11].cpu().numpy()), n_rays
+
+
+def step_params(steps: int = 1, seed: int = 0, shutter=(0.0, 1.0), background=(0.0, 0.0, 0.0), flags: int = 0) -> StepParams:
+    """hrt_step_params: the rounds per call, query_params' seed and shutter, scatter_params' background, STEP_* flags."""
+    return StepParams(flags, steps, float(shutter[0]), float(shutter[1]), seed, _F3(*[float(x) for x in background]), 0)
+
+
+def trace_paths_fused(scene: "Scene", cam: Camera, p: RenderParams, tiles=None, device: bool = False, steps: int = 2,
+                      check_every: int = 4):
+    """trace_paths through the fused call: camera paths, then Scene.step over two ping-pong live lists that stay on the
+    device, `steps` rounds per call.  The live count is read back every `check_every` calls only (0: never, the loop then
+    makes all ceil(p.max_depth / steps) calls, the late ones over an empty list), the ray count once at the end.  Returns
+    what trace_paths returns, bit for bit."""
+    import torch
+
+    rays, paths = camera_paths(scene, cam, p, tiles, device=True)
+    n = rays.shape[0]
+    lists = [(torch.empty(n, dtype=torch.int32, device=rays.device), torch.zeros(1, dtype=torch.int32, device=rays.device))
+             for _ in range(2)]
+    n_rays = torch.zeros(1, dtype=torch.int64, device=rays.device)
+    live = None
+    for call in range((p.max_depth + steps - 1) // steps):
+        out = lists[call & 1]
+        scene.step(rays, paths, steps=steps, seed=p.seed, shutter=(cam.time0, cam.time1), background=tuple(p.background),
+                   live=live, live_out=out, n_rays=n_rays)
+        live = out
+        if check_every and (call + 1) % check_every == 0 and int(out[1]) == 0:
+            break
+    return (paths if device else paths[:, 8:11].cpu().numpy()), int(n_rays)
 
 
 def tile_grid(width: int, height: int, tile_size: int = 80, rank: int = 0, world: int = 1) -> List[Tuple[int, int, int, int]]:

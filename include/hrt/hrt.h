@@ -862,6 +862,74 @@ hrt_status hrt_camera_paths(hrt_scene* s, const hrt_camera* cam, const hrt_rende
 hrt_status hrt_camera_paths_host(hrt_scene* s, const hrt_camera* cam, const hrt_render_params* p, const hrt_tile* tiles,
                                  uint32_t n_tiles, hrt_ray* rays, hrt_path* paths);
 
+/* ---- path stepping: intersect and scatter fused, over live lists kept on the device ----
+ * hrt_scene_step does for every path of its DOMAIN, in registers, what hrt_scene_intersect followed by hrt_scene_scatter
+ * does, `steps` times over, and can write the indices of the paths still live into a device list that the next call takes
+ * as its domain: a wavefront loop with no hit records in memory, no pass over finished records and no host round trip
+ * (examples/render_wavefront.c; hrt.trace_paths_fused in the Python binding).
+ *
+ *   1. Domain.  in == NULL: every i in [0, n).  Otherwise the first min(*in->d_count, in->capacity) entries of
+ *      in->d_index; the count is read on the device, in stream order.  An entry >= n is skipped and never dereferenced.
+ *      Entries must be distinct: with duplicates the records of a duplicated index are unspecified (nothing outside the
+ *      arrays is touched).
+ *   2. A path DONE on entry: nothing of ray i, path i or hit i is written, and i is not put into `out`.
+ *   3. Otherwise, up to `steps` times while the path is not DONE (csrc/step.h step_path): hit = hrt_scene_intersect's
+ *      answer for the ray with (seed, time0, time1, flags), the invalid-ray record included; then hrt_scene_scatter's rules
+ *      2 to 5 on (ray, hit, path, background), the refusals included (an all-zero rng, depth_left == 0, and an invalid
+ *      hit, which ends the path INVALID).  No arithmetic is new: ray i and path i after the call are, bit for bit, those
+ *      after `steps` rounds of the two calls.
+ *      What a result depends on.  A record after the call is a function of that record before it, the params and the
+ *      committed scene ALONE: never of n, of the domain, of the order of the list, of `steps` being split over several
+ *      calls, of HRT_STEP_NO_LDS, of where the kernel keeps the Perlin tables (HRT_SCATTER_PERLIN_LDS=0), of the claim
+ *      size (HRT_QUERY_CLAIM) or of the device.
+ *   4. d_hits, when given: hits[i] is the hit of the LAST intersect the call made for path i (with steps == 1:
+ *      hrt_scene_intersect's hit of the ray as it was on entry).  For i outside the domain, or DONE on entry, it is not
+ *      written.
+ *   5. out, when given: the call sets *out->d_count to 0 in stream order and then appends each i of the domain that was
+ *      not DONE on entry and is not DONE after the call, exactly once.  The order is unspecified; the set and the count
+ *      are deterministic.  out->capacity >= (in ? in->capacity : n) is checked; out must share neither pointer with in.
+ *   6. d_n_rays, when given (8-byte aligned): the call ADDS the number of valid rays it walked, that is rays of live
+ *      paths that are no invalid ray.  Summed over a run to completion it is the render's hrt_render_stats.segments.
+ *      The caller zeroes it.
+ *   7. Records outside the domain, and records [n ..), are never written.
+ *   8. The call writes nothing in the scene, is re-entrant as the renders are and asynchronous on `stream`; it allocates
+ *      its claim counter in stream order, as hrt_scene_intersect does.
+ * d_rays, d_paths and d_hits are device memory, n records of 48 bytes each, 16-byte aligned, none overlapping.  An
+ * hrt_path_list is a HOST struct of DEVICE pointers: `capacity` u32 entries at d_index and one u32 at d_count, both 4-byte
+ * aligned.
+ * Errors, each changing nothing and answered before any device call: HRT_ERR_INVALID_ARG for a null scene, params, rays or
+ * paths, a misaligned buffer, unknown flags, steps == 0, reserved != 0, time0 <= time1 not holding or a non-finite bound,
+ * a non-finite background component, n >= 2^32, a list with a null pointer, a misaligned pointer or reserved != 0, `out`
+ * too small or sharing a pointer with `in`; HRT_ERR_STATE for an uncommitted scene.  n == 0 is HRT_OK whatever the record
+ * buffers, launches no kernel and still sets a given *out->d_count to 0. */
+enum {
+  HRT_STEP_SKIP_MEDIA = 1,    /* the HRT_QUERY_* meanings and values */
+  HRT_STEP_NO_LDS = 2,        /* the scene and the Perlin tables stay in global memory (A/B; the same records) */
+  HRT_STEP_REFERENCE_CULL = 4
+};
+typedef struct hrt_step_params hrt_step_params;
+struct hrt_step_params { /* 40 bytes */
+  uint32_t flags;        /* HRT_STEP_* bits */
+  uint32_t steps;        /* >= 1: rounds a live path makes inside the call */
+  float time0, time1;    /* as hrt_query_params */
+  uint64_t seed;         /* as hrt_query_params */
+  float background[3];   /* as hrt_scatter_params; finite */
+  uint32_t reserved;     /* 0 */
+};
+typedef struct hrt_path_list hrt_path_list;
+struct hrt_path_list { /* 24 bytes: a HOST struct of DEVICE pointers */
+  uint32_t* d_index;   /* capacity entries, 4-byte aligned */
+  uint32_t* d_count;   /* one u32 in device memory */
+  uint32_t capacity, reserved; /* reserved: 0 */
+};
+hrt_status hrt_scene_step(hrt_scene* s, const hrt_step_params* sp, hrt_ray* d_rays, hrt_path* d_paths, uint64_t n,
+                          hrt_hit* d_hits /* may be NULL */, const hrt_path_list* in /* NULL: every i in [0, n) */,
+                          const hrt_path_list* out /* may be NULL */, uint64_t* d_n_rays /* may be NULL */, void* stream);
+/* ... with rays, paths, hits and the ray count in HOST memory: the domain is [0, n), there are no lists; copies in, runs
+ * the device path on the scene's device, copies rays, paths (and hits) out and ADDS to *n_rays; synchronous */
+hrt_status hrt_scene_step_host(hrt_scene* s, const hrt_step_params* sp, hrt_ray* rays, hrt_path* paths, uint64_t n,
+                               hrt_hit* hits /* may be NULL */, uint64_t* n_rays /* may be NULL */);
+
 /* ---- diagnostics ---- */
 /* Device occupancy / layout facts of the committed scene (for DESIGN/bench). */
 typedef struct hrt_scene_info {
