@@ -699,8 +699,13 @@ hrt_status hrt_accum_merge_tiles(hrt_accum* dst, const hrt_accum* src, void* str
  *   origin, direction and time computes it: the walk the feature pass makes (lane.h trace over the reference node
  *   stream from t_min, the closest starting at t_max), then the hit record (lane.h make_record; hit_record.rs).  The
  *   interval is the reference's at both ends: a root t is refused when t < t_min or t_max < t (sphere.rs:53-55,
- *   moving_sphere.rs:74-76, rect.rs:61), so t == t_min and t == t_max are both accepted, and a later primitive
- *   replaces an earlier one at an equal t.  The direction is used as given (t is in units of its length).
+ *   moving_sphere.rs:74-76, rect.rs:61), so t == t_min and t == t_max are both accepted by the primitive, and a later
+ *   primitive replaces an earlier one at an equal t.  The reference asks a primitive only after its boxes
+ *   (bvh_node.rs:104-106), and aabb.rs refuses a box when `t_max <= t_min` holds of its clipped interval: a rect lies in
+ *   the face of its own box (the 0.0002-thick slab of rect.rs:97-107, a Cuboid's box), whose entry time (bound - o) * (1 / d)
+ *   can round onto the rect's t = (k - o) / d or past it, so a rect's hit at exactly t_max or t_min can be the
+ *   reference's miss, and is then a miss here (measured: 0 to 4% of such rays on scenes with rects, none on spheres;
+ *   DESIGN.md "Queries against the oracle").  The direction is used as given (t is in units of its length).
  *   Culling.  Boxes are culled by the scene's exact mode (the reference's box test plus culling that provably drops
  *   no accepted hit) when [time0, time1] of the params lies inside the interval the scene's BVH boxes were built for,
  *   and by the reference's test alone otherwise or under HRT_QUERY_REFERENCE_CULL.  Both give the same hits; there is
@@ -708,14 +713,22 @@ hrt_status hrt_accum_merge_tiles(hrt_accum* dst, const hrt_accum* src, void* str
  *   The record.  t, point, normal, u, v and the front-face bit are the hit record's; the normal faces the ray.  u and
  *   v are ALWAYS computed (a render computes a sphere's only under an image texture).
  *   Ids.  prim is the primitive's index in reference pre-order (hrt_debug_prim_record order 0), for sphere scenes and
- *   general scenes alike; material is the material's id.  A scatter inside a ConstantMedium sets HRT_HIT_MEDIUM:
- *   prim is then the medium's index (creation order of the flattened scene), normal (0, 0, 0), u = v = 0 and front clear, as a
- *   render's record has it.
+ *   general scenes alike: the pre-order of world.hit's recursion (left before right, a Cuboid's six sides in their list
+ *   order, through instances) over the primitives OUTSIDE every medium boundary; the boundaries' own primitives are
+ *   numbered after all of those and no record names one.  material is the material's id: a constructor's id, or for a
+ *   medium's phase function the number of constructed materials plus the medium's index.  A scatter inside a
+ *   ConstantMedium sets HRT_HIT_MEDIUM: prim is then the medium's index, which counts the ConstantMedium nodes in that
+ *   same pre-order (NOT in creation order, which is the medium id that keys the draws below), normal (0, 0, 0),
+ *   u = v = 0 and front clear, as a render's record has it.
  *   Medium draws.  A ConstantMedium draws its scatter distance from the sub-stream keyed by (params.seed, ray.pixel,
  *   ray.sample, ray.segment, medium id), exactly a render's key for segment number `segment` of sample `sample` (the
  *   ABSOLUTE sample index) of pixel `pixel` (y * width + x): a query with a path's key repeats that segment's draw.
  *   HRT_QUERY_SKIP_MEDIA makes every medium transparent.
  *   Miss.  flags = 0, t = the ray's t_max, prim = material = 0xFFFFFFFF, every other field +0.
+ *   Non-finite records.  A valid ray can still take the reference's arithmetic to a NaN: a ray in a rect's plane
+ *   (t = 0 / 0), a direction of length 1e18 (sphere.rs's half_b^2 - a c = inf - inf), an origin so far away that
+ *   (at(root) - center) / radius leaves [-1, 1] and sphere.rs's acos gives a NaN v.  Such a record is the reference's,
+ *   field by field: a field that is NaN there is a NaN here, of unspecified sign and payload; every other field is equal.
  *   Invalid ray.  A ray with a non-finite value in origin, direction, time or t_min, with a NaN t_max, with the
  *   direction (0, 0, 0), for which t_min < t_max does not hold, or whose time lies outside [time0, time1], is not
  *   traced: flags = HRT_HIT_INVALID, prim = material = 0xFFFFFFFF, every other field +0.

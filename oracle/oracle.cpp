@@ -27,6 +27,7 @@
 #include <memory>
 #include <stdexcept>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 using namespace hrt;
@@ -90,6 +91,7 @@ struct Ray {
 };
 
 struct Material;
+struct Hittable;
 
 /* ---------------------------------------------------------------- hit_record.rs:11-29 */
 struct HitRecord {
@@ -97,6 +99,7 @@ struct HitRecord {
   float t, u, v;
   bool front_face;
   const Material* material;
+  const Hittable* prim = nullptr; /* not the reference's: the leaf that wrote the record (oracle_scene_hit's ids) */
   void set_face_normal(const Ray& ray, Vec3 outward_normal) {
     front_face = dot(ray.direction, outward_normal) < 0.0f;
     normal = front_face ? outward_normal : -outward_normal;
@@ -360,12 +363,35 @@ struct Isotropic : Material {
   }
 };
 
+/* The oracle's own numbering of a world (oracle_scene_hit's ids; not the reference's): one recursive pre-order pass
+ * at build time, left before right, a Cuboid's sides in their list order, through instances and medium boundaries.
+ * kind 0 sphere (p: c3 r), 1 moving sphere (p: c0 c1 t0 t1 r), 2 rect (p: plane a0 a1 b0 b1 k), as oracle_prim_hit. */
+static const uint32_t NO_ID = 0xFFFFFFFFu;
+struct PrimInfo {
+  uint32_t kind, boundary_of; /* boundary_of: the medium_id of the ConstantMedium whose boundary holds it, or NO_ID */
+  float p[9];
+};
+struct Numbering {
+  std::unordered_map<const Hittable*, uint32_t> prim; /* leaf -> pre-order index */
+  std::vector<PrimInfo> info;                          /* by pre-order index */
+  std::vector<const Hittable*> media;                  /* the ConstantMedium nodes in pre-order */
+  uint32_t inside = NO_ID;
+  void leaf(const Hittable* h, uint32_t kind, std::initializer_list<float> p) {
+    PrimInfo pi{kind, inside, {}};
+    int i = 0;
+    for (float x : p) pi.p[i++] = x;
+    prim[h] = (uint32_t)info.size();
+    info.push_back(pi);
+  }
+};
+
 /* ---------------------------------------------------------------- hittable/mod.rs:19-25 */
 struct Hittable {
   virtual ~Hittable() {}
   virtual bool hit(const Ray& ray, float tmin, float tmax, HitRecord& rec, Ctx& ctx) const = 0;
   virtual bool bounding_box(float t0, float t1, Aabb& out) const = 0;
   virtual uint32_t count() const = 0;
+  virtual void number(Numbering& N) const = 0;
 };
 using HitP = std::unique_ptr<Hittable>;
 
@@ -402,6 +428,7 @@ struct Sphere : Hittable {
     rec.point = ray.at(root);
     rec.t = root;
     rec.material = material.get();
+    rec.prim = this;
     rec.set_face_normal(ray, outward_normal);
     return true;
   }
@@ -412,6 +439,7 @@ struct Sphere : Hittable {
     return true;
   }
   uint32_t count() const override { return 1; }
+  void number(Numbering& N) const override { N.leaf(this, 0, {center.x, center.y, center.z, radius}); }
 };
 
 /* moving_sphere.rs:50-114 */
@@ -445,6 +473,7 @@ struct MovingSphere : Hittable {
     rec.point = ray.at(root);
     rec.t = root;
     rec.material = material.get();
+    rec.prim = this;
     rec.set_face_normal(ray, outward_normal);
     return true;
   }
@@ -456,6 +485,10 @@ struct MovingSphere : Hittable {
     return true;
   }
   uint32_t count() const override { return 1; }
+  void number(Numbering& N) const override {
+    N.leaf(this, 1, {center_start.x, center_start.y, center_start.z, center_end.x, center_end.y, center_end.z, time_start,
+                     time_end, radius});
+  }
 };
 
 /* rect.rs:19-108 */
@@ -481,6 +514,7 @@ struct Rect : Hittable {
     rec.u = (a - a0) / (a1 - a0);
     rec.v = (b - b0) / (b1 - b0);
     rec.material = material.get();
+    rec.prim = this;
     Vec3 outward = v3(0.0f, 0.0f, 0.0f);
     outward[k_axis] = 1.0f;
     rec.set_face_normal(ray, outward);
@@ -493,6 +527,7 @@ struct Rect : Hittable {
     return true;
   }
   uint32_t count() const override { return 1; }
+  void number(Numbering& N) const override { N.leaf(this, 2, {(float)plane, a0, a1, b0, b1, k}); }
 };
 
 /* list.rs:9-49 */
@@ -529,6 +564,9 @@ struct List : Hittable {
     for (const auto& o : objects) n += o->count();
     return n;
   }
+  void number(Numbering& N) const override {
+    for (const auto& o : objects) o->number(N);
+  }
 };
 
 /* cuboid.rs:22-110: a List of 6 rects in this order */
@@ -553,6 +591,7 @@ struct Cuboid : Hittable {
     return true;
   }
   uint32_t count() const override { return sides->count(); }
+  void number(Numbering& N) const override { sides->number(N); }
 };
 
 /* translation.rs:9-53 */
@@ -574,6 +613,7 @@ struct Translation : Hittable {
     return true;
   }
   uint32_t count() const override { return hittable->count(); }
+  void number(Numbering& N) const override { hittable->number(N); }
 };
 
 /* rotation.rs:10-143 */
@@ -642,6 +682,7 @@ struct Rotation : Hittable {
     return true;
   }
   uint32_t count() const override { return 1; }
+  void number(Numbering& N) const override { hittable->number(N); }
 };
 
 /* constant_medium.rs:17-85 */
@@ -676,12 +717,20 @@ struct ConstantMedium : Hittable {
     rec.v = 0.0f;
     rec.front_face = false;
     rec.material = phase_function.get();
+    rec.prim = this;
     return true;
   }
   bool bounding_box(float t0, float t1, Aabb& out) const override {
     return boundary->bounding_box(t0, t1, out);
   }
   uint32_t count() const override { return boundary->count(); }
+  void number(Numbering& N) const override {
+    N.media.push_back(this);
+    const uint32_t outer = N.inside;
+    N.inside = medium_id;
+    boundary->number(N);
+    N.inside = outer;
+  }
 };
 
 /* bvh_node.rs:10-139 */
@@ -752,6 +801,11 @@ struct BvhNode : Hittable {
   }
   bool bounding_box(float, float, Aabb& out) const override { out = box; return true; }
   uint32_t count() const override { return leaf ? leaf->count() : left->count() + right->count(); }
+  void number(Numbering& N) const override {
+    if (leaf) { leaf->number(N); return; }
+    left->number(N);
+    right->number(N);
+  }
 };
 
 /* ---------------------------------------------------------------- camera.rs:16-96 */
@@ -806,7 +860,21 @@ struct Scene {
   HitP world;
   PresetInfo info;
   uint32_t n_media = 0;
+  /* oracle_scene_hit's ids (finish_ids below).  mats: a description's materials in creation order, empty for a preset,
+   * whose records then carry no material id; the media's phase functions follow them in the media's pre-order. */
+  Numbering num;
+  std::vector<MatP> mats;
+  std::vector<const Material*> mat_by_id;
+  std::unordered_map<const Material*, uint32_t> mat_id;
 };
+
+static void finish_ids(Scene& sc) {
+  sc.world->number(sc.num);
+  if (sc.mats.empty()) return;
+  for (const auto& m : sc.mats) sc.mat_by_id.push_back(m.get());
+  for (const Hittable* h : sc.num.media) sc.mat_by_id.push_back(static_cast<const ConstantMedium*>(h)->phase_function.get());
+  for (size_t i = 0; i < sc.mat_by_id.size(); i++) sc.mat_id[sc.mat_by_id[i]] = (uint32_t)i;
+}
 
 static TexP solid(float r, float g, float b) { return std::make_shared<SolidColor>(v3(r, g, b)); }
 static MatP lambert(TexP t) { return std::make_shared<Lambertian>(std::move(t)); }
@@ -1130,6 +1198,7 @@ static Scene* build_preset(int preset, uint64_t seed, const uint8_t* img, uint32
       throw std::runtime_error("unknown preset");
   }
   sc->n_media = B.n_media;
+  finish_ids(*sc);
   return sc.release();
 }
 
@@ -1280,6 +1349,8 @@ static Scene* build_desc(const uint32_t* words, uint64_t n_words, const uint8_t*
   I.focus_dist = u2f(h[11]);
   I.time0 = u2f(h[12]);
   I.time1 = u2f(h[13]);
+  sc->mats = mats;
+  finish_ids(*sc);
   return sc.release();
 }
 
@@ -1537,6 +1608,120 @@ int oracle_render_rows_cam(void* scene, const float* cam11, uint32_t W, uint32_t
   }
   return render_rows_with(scene, cam11, W, H, spp, depth, sample_offset, seed, t_min, rows, n_rows, x0, w, task_w,
                           out, nthreads, counters);
+}
+
+/* ---- single calls of the world and of a material (tests/test_query_oracle.py, tests/test_scatter_oracle.py) ----
+ * oracle_scene_hit: world->hit(ray, t_min, t_max) for n rays of 12 words each
+ *     origin(3) direction(3) time t_min t_max pixel sample segment
+ * with ctx.pkey = path_key(seed, pixel, sample) and ctx.segment = segment; no validity rule.  Per ray 16 words:
+ *     hit(0/1) t point(3) normal(3) u v front_face(0/1) medium(0/1) material prim medium_id 0
+ * material: the index of rec.material among the description's materials (a medium's phase function: see Scene), NO_ID in
+ * a preset; prim: the leaf's pre-order index (NO_ID for a medium's record); medium_id: the ConstantMedium's, else NO_ID.
+ * A miss is all zero but for the three ids, which are NO_ID. */
+int oracle_scene_hit(void* scene, const uint32_t* rays, uint64_t n, uint64_t seed, uint32_t* out) {
+  try {
+    Scene* s = static_cast<Scene*>(scene);
+    if (!s || (n && (!rays || !out))) throw std::runtime_error("bad hit arguments");
+    Counters cnt;
+    for (uint64_t i = 0; i < n; i++) {
+      const uint32_t* r = rays + 12 * i;
+      uint32_t* o = out + 16 * i;
+      Ray ray{v3(u2f(r[0]), u2f(r[1]), u2f(r[2])), v3(u2f(r[3]), u2f(r[4]), u2f(r[5])), u2f(r[6])};
+      Ctx ctx;
+      ctx.cnt = &cnt;
+      ctx.pkey = path_key(seed, r[9], r[10]);
+      ctx.rng = rng_from_key(ctx.pkey);
+      ctx.segment = r[11];
+      HitRecord rec;
+      memset(o, 0, 16 * sizeof(uint32_t));
+      o[12] = o[13] = o[14] = NO_ID;
+      if (!s->world->hit(ray, u2f(r[7]), u2f(r[8]), rec, ctx)) continue;
+      o[0] = 1;
+      const float v[9] = {rec.t, rec.point.x, rec.point.y, rec.point.z, rec.normal.x, rec.normal.y, rec.normal.z, rec.u, rec.v};
+      for (int k = 0; k < 9; k++) o[1 + k] = f2u(v[k]);
+      o[10] = rec.front_face ? 1u : 0u;
+      auto m = s->mat_id.find(rec.material);
+      if (m != s->mat_id.end()) o[12] = m->second;
+      auto p = s->num.prim.find(rec.prim);
+      if (p != s->num.prim.end()) {
+        o[13] = p->second;
+      } else {
+        o[11] = 1;
+        o[14] = static_cast<const ConstantMedium*>(rec.prim)->medium_id;
+      }
+    }
+    return 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return 1;
+  }
+}
+
+/* The numbered leaves: up to cap records of 12 words (kind, boundary_of, p[9], 0) in pre-order; returns their number. */
+uint32_t oracle_scene_prims(void* scene, uint32_t* out, uint32_t cap) {
+  const Scene* s = static_cast<Scene*>(scene);
+  const uint32_t n = (uint32_t)s->num.info.size();
+  for (uint32_t i = 0; i < n && i < cap; i++) {
+    const PrimInfo& pi = s->num.info[i];
+    uint32_t* o = out + 12 * i;
+    o[0] = pi.kind;
+    o[1] = pi.boundary_of;
+    for (int k = 0; k < 9; k++) o[2 + k] = f2u(pi.p[k]);
+    o[11] = 0;
+  }
+  return n;
+}
+
+/* The media in pre-order: medium_id of each (up to cap); returns their number. */
+uint32_t oracle_scene_media(void* scene, uint32_t* out, uint32_t cap) {
+  const Scene* s = static_cast<Scene*>(scene);
+  const uint32_t n = (uint32_t)s->num.media.size();
+  for (uint32_t i = 0; i < n && i < cap; i++) out[i] = static_cast<const ConstantMedium*>(s->num.media[i])->medium_id;
+  return n;
+}
+
+/* oracle_scatter: one ray_color step after the hit (application.rs:486-494) at material `material` of the scene:
+ * emitted(u, v, point), then scatter(ray, rec), drawing from the xoshiro state rng[4].
+ *   ray: origin(3) direction(3) time;  rec: t point(3) normal(3) u v front_face, as oracle_prim_hit writes it
+ *   out, 18 words: emitted(3) scattered(0/1) attenuation(3) origin(3) direction(3) time, then the rng state afterwards
+ * Not scattered: attenuation and the scattered ray read +0. */
+int oracle_scatter(void* scene, uint32_t material, const float* ray, const float* rec10, const uint32_t* rng, uint32_t* out) {
+  try {
+    Scene* s = static_cast<Scene*>(scene);
+    if (!s || !ray || !rec10 || !rng || !out) throw std::runtime_error("bad scatter arguments");
+    if (material >= s->mat_by_id.size()) throw std::runtime_error("bad material id");
+    const Material* m = s->mat_by_id[material];
+    Counters cnt;
+    Ctx ctx;
+    ctx.cnt = &cnt;
+    ctx.rng.s0 = rng[0], ctx.rng.s1 = rng[1], ctx.rng.s2 = rng[2], ctx.rng.s3 = rng[3];
+    Ray in{v3(ray[0], ray[1], ray[2]), v3(ray[3], ray[4], ray[5]), ray[6]};
+    HitRecord rec;
+    rec.t = rec10[0];
+    rec.point = v3(rec10[1], rec10[2], rec10[3]);
+    rec.normal = v3(rec10[4], rec10[5], rec10[6]);
+    rec.u = rec10[7];
+    rec.v = rec10[8];
+    rec.front_face = rec10[9] != 0.0f;
+    rec.material = m;
+    Vec3 emitted = m->emitted(rec.u, rec.v, rec.point, ctx);
+    Vec3 att = v3(0.0f, 0.0f, 0.0f);
+    Ray sc{v3(0.0f, 0.0f, 0.0f), v3(0.0f, 0.0f, 0.0f), 0.0f};
+    const bool scattered = m->scatter(in, rec, att, sc, ctx);
+    if (!scattered) {
+      att = v3(0.0f, 0.0f, 0.0f);
+      sc = Ray{v3(0.0f, 0.0f, 0.0f), v3(0.0f, 0.0f, 0.0f), 0.0f};
+    }
+    const float v[14] = {emitted.x, emitted.y, emitted.z, 0.0f, att.x, att.y, att.z, sc.origin.x, sc.origin.y, sc.origin.z,
+                         sc.direction.x, sc.direction.y, sc.direction.z, sc.time};
+    for (int k = 0; k < 14; k++) out[k] = f2u(v[k]);
+    out[3] = scattered ? 1u : 0u;
+    out[14] = ctx.rng.s0, out[15] = ctx.rng.s1, out[16] = ctx.rng.s2, out[17] = ctx.rng.s3;
+    return 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return 1;
+  }
 }
 
 /* ---- unit entry points for the KAT fixtures (tests/golden) ---- */

@@ -66,12 +66,33 @@ def load() -> ctypes.CDLL:
     L.oracle_set_libm.argtypes = [i32]
     L.oracle_record_math.argtypes = [vp, u32, vp]
     L.oracle_rng.argtypes = [u64, u32, u32, i32, u32, vp]
+    L.oracle_scene_hit.restype = i32
+    L.oracle_scene_hit.argtypes = [vp, vp, u64, u64, vp]
+    L.oracle_scene_prims.restype = u32
+    L.oracle_scene_prims.argtypes = [vp, vp, u32]
+    L.oracle_scene_media.restype = u32
+    L.oracle_scene_media.argtypes = [vp, vp, u32]
+    L.oracle_scatter.restype = i32
+    L.oracle_scatter.argtypes = [vp, u32, vp, vp, vp, vp]
     _lib = L
     return L
 
 
 def _p(a):
     return a.ctypes.data
+
+
+NO_ID = 0xFFFFFFFF
+_F, _U = np.float32, np.uint32
+# oracle.cpp oracle_scene_hit's records, oracle_scene_prims' and oracle_scatter's
+RAY = np.dtype([("origin", _F, 3), ("direction", _F, 3), ("time", _F), ("t_min", _F), ("t_max", _F), ("pixel", _U), ("sample", _U),
+                ("segment", _U)])
+HIT = np.dtype([("hit", _U), ("t", _F), ("point", _F, 3), ("normal", _F, 3), ("u", _F), ("v", _F), ("front_face", _U), ("medium", _U),
+                ("material", _U), ("prim", _U), ("medium_id", _U), ("pad", _U)])
+PRIM = np.dtype([("kind", _U), ("boundary_of", _U), ("p", _F, 9), ("pad", _U)])
+SCATTER = np.dtype([("emitted", _F, 3), ("scattered", _U), ("attenuation", _F, 3), ("origin", _F, 3), ("direction", _F, 3), ("time", _F),
+                    ("rng", _U, 4)])
+assert RAY.itemsize == 48 and HIT.itemsize == 64 and PRIM.itemsize == 48 and SCATTER.itemsize == 72
 
 
 def _cam11(camera) -> np.ndarray:
@@ -130,6 +151,48 @@ class OracleScene:
     def bbox(self):
         b = np.zeros(6, np.float32)
         return b if load().oracle_scene_bbox(self.h, _p(b)) else None
+
+    def hit(self, rays: np.ndarray, seed: int = 0) -> np.ndarray:
+        """world.hit(ray, t_min, t_max) of every RAY record, with the media's draws keyed by (seed, pixel, sample,
+        segment): HIT records.  No validity rule: a NaN goes where the reference's arithmetic takes it."""
+        r = np.ascontiguousarray(rays, RAY).reshape(-1)
+        out = np.zeros(r.size, HIT)
+        if load().oracle_scene_hit(self.h, _p(r), r.size, seed, _p(out)) != 0:
+            raise RuntimeError(load().oracle_last_error().decode())
+        return out
+
+    def prims(self) -> np.ndarray:
+        """The world's leaves in the oracle's pre-order: PRIM records (kind and p as oracle_prim_hit takes them)."""
+        n = load().oracle_scene_prims(self.h, None, 0)
+        out = np.zeros(max(n, 1), PRIM)
+        load().oracle_scene_prims(self.h, _p(out), n)
+        return out[:n]
+
+    def media(self) -> np.ndarray:
+        """medium_id of the world's ConstantMedium nodes in pre-order (their phase functions' material ids follow the
+        description's materials in this order)."""
+        n = load().oracle_scene_media(self.h, None, 0)
+        out = np.zeros(max(n, 1), np.uint32)
+        load().oracle_scene_media(self.h, _p(out), n)
+        return out[:n]
+
+    def scatter(self, material, rays: np.ndarray, hits: np.ndarray, rng: np.ndarray) -> np.ndarray:
+        """emitted(u, v, point) and then scatter(ray, rec) of material[i] for ray i (RAY) and record i (HIT), drawing from
+        the xoshiro state rng[i] (4 words): SCATTER records, the state afterwards included."""
+        r = np.ascontiguousarray(rays, RAY).reshape(-1)
+        h = np.ascontiguousarray(hits, HIT).reshape(-1)
+        g = np.ascontiguousarray(rng, np.uint32).reshape(-1, 4)
+        m = np.broadcast_to(np.asarray(material, np.uint32), r.shape)
+        out = np.zeros(r.size, SCATTER)
+        L = load()
+        ray7, rec10 = np.zeros(7, np.float32), np.zeros(10, np.float32)
+        for i in range(r.size):
+            ray7[0:3], ray7[3:6], ray7[6] = r["origin"][i], r["direction"][i], r["time"][i]
+            rec10[0], rec10[1:4], rec10[4:7] = h["t"][i], h["point"][i], h["normal"][i]
+            rec10[7], rec10[8], rec10[9] = h["u"][i], h["v"][i], 1.0 if h["front_face"][i] else 0.0
+            if L.oracle_scatter(self.h, int(m[i]), _p(ray7), _p(rec10), _p(g[i:i + 1]), _p(out[i:i + 1])) != 0:
+                raise RuntimeError(L.oracle_last_error().decode())
+        return out
 
     def render(self, width, height, spp, depth=50, seed=1, region=None, threads=8, sample_offset=0, t_min=0.001,
                camera=None):
