@@ -265,7 +265,12 @@ hrt_status hrt_camera_init(hrt_camera* cam, const float look_from[3], const floa
  * Errors of the launch itself: with stats, HRT_ERR_STATE when the walk watchdog stopped walks that
  * could not end (corrupt scene data; the frame is incomplete).  Without stats the call returns before
  * the kernel ends; such a launch is then reported as HRT_ERR_STATE by the first later call on the
- * scene that finds it finished (the next hrt_render_* call, or hrt_scene_synchronize). */
+ * scene that finds it finished (the next hrt_render_* call, or hrt_scene_synchronize).  That report belongs to
+ * the scene, not to a thread: with several threads on one scene it goes to whichever call sees the launch first,
+ * on whatever thread, and to that call alone.
+ * Threads: the launches of one scene are issued one at a time (a call holds the scene's launch lock while it
+ * enqueues, and a call with stats until its kernel has ended); the kernels of different calls still overlap on
+ * their streams.  Results never depend on which other calls are in flight. */
 hrt_status hrt_render_tiles_device(hrt_scene* s, const hrt_camera* cam, const hrt_render_params* p,
                                    const hrt_tile* tiles, uint32_t n_tiles, float* d_rgba,
                                    void* stream, hrt_render_stats* stats);
