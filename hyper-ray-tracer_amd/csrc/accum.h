@@ -21,13 +21,14 @@
 namespace hrt {
 namespace accum {
 
-/* A pass's sum of pixel i: partial is [n_chunks][n] records with the sum in .x .y .z (float4 on both sides). */
-template <class F4>
-HRT_HD Vec3 pass_sum(const F4* partial, uint32_t n_chunks, size_t n, size_t i) {
-  const F4 a = partial[i];
+/* A pass's sum of pixel i: partial is [n_chunks][n] records with the sum in .x .y .z (float4 on both sides), a pointer
+ * or anything indexed like one (accum_paths.h PathChunks, which makes each chunk sum when it is asked for). */
+template <class Partial>
+HRT_HD Vec3 pass_sum(const Partial& partial, uint32_t n_chunks, size_t n, size_t i) {
+  const auto a = partial[i];
   Vec3 sum = v3(a.x, a.y, a.z);
   for (uint32_t c = 1; c < n_chunks; c++) {
-    const F4 b = partial[(size_t)c * n + i];
+    const auto b = partial[(size_t)c * n + i];
     sum = sum + v3(b.x, b.y, b.z);
   }
   return sum;
@@ -76,12 +77,12 @@ HRT_HD float luma(Vec3 s) { return (s.x + s.y) + s.z; }
 HRT_HD float chunk_term(float y, uint32_t n_c) { return (y * y) * (1.0f / (float)n_c); }
 
 /* A pass's moment of pixel i: partial as for pass_sum, count_of(c) = the samples of chunk c. */
-template <class F4, class CountOf>
-HRT_HD float pass_moment(const F4* partial, uint32_t n_chunks, size_t n, size_t i, CountOf count_of) {
-  const F4 a = partial[i];
+template <class Partial, class CountOf>
+HRT_HD float pass_moment(const Partial& partial, uint32_t n_chunks, size_t n, size_t i, CountOf count_of) {
+  const auto a = partial[i];
   float m = chunk_term(luma(v3(a.x, a.y, a.z)), count_of(0u));
   for (uint32_t c = 1; c < n_chunks; c++) {
-    const F4 b = partial[(size_t)c * n + i];
+    const auto b = partial[(size_t)c * n + i];
     m = m + chunk_term(luma(v3(b.x, b.y, b.z)), count_of(c));
   }
   return m;

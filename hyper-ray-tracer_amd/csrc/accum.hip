@@ -13,9 +13,11 @@
 
 #include "accum.h"
 #include "accum_ledger.h"
+#include "accum_paths.h"
 #include "accum_snapshot.h"
 #include "feature_pass.h"
 #include "filter.h"
+#include "query_host.h"
 #include "render_host.h"
 #include "tile_reduce.h"
 
@@ -101,6 +103,97 @@ __global__ __launch_bounds__(256) void accumulate_chunks(const float4* __restric
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     if constexpr (MOMENTS) accumulate_pixel_mapped<FORMAT>(partial, acc, n, n_chunks, scale, out, i, M);
     else accumulate_pixel<FORMAT>(partial, acc, n, n_chunks, scale, out, i);
+  }
+}
+
+/* ---- caller-traced paths into the accumulator (hrt_accum_add_paths; arithmetic: accum_paths.h).  A path is three
+ * float4s and the pass reads the last of each: the radiance and the flags.  One launch, no partial buffer. */
+constexpr uint32_t PATHS_BLOCK = 256;
+constexpr uint32_t PATHS_STAGE = 2048; /* 16-B slots of accumulate_paths' staging buffer: 32 KB, five workgroups a CU */
+struct PathArgs {
+  const float4* paths; /* n_px x samples records of three float4s, a pixel's consecutive */
+  float4* acc;
+  float* m2;  /* null: the accumulator keeps no noise plane */
+  void* out;  /* FORMAT >= 0: the frame after the pass, at `scale` */
+  float scale;
+  const G::TileDev* tiles; /* launch pixel -> accumulator pixel (mapped_pixel); n_tiles = 0: onto itself */
+  uint32_t n_tiles;
+  uint32_t n_px, samples, n_chunks;
+  accum::PathSchedule schedule;
+  uint32_t* live; /* null, or takes the number of records that are not PATH_DONE */
+  uint32_t run, pitch; /* staged kernel: pixels a workgroup stages per trip, slots from a pixel's row to the next */
+};
+/* a pixel's records where the caller left them, and their last 16 bytes staged in LDS */
+struct GlobalRecords {
+  const float4* first;
+  __host__ __device__ float4 operator()(uint32_t k) const { return first[3 * (size_t)k + 2]; }
+};
+__host__ __device__ inline uint32_t path_not_done(const float4& tail) {
+  uint32_t flags;
+  memcpy(&flags, &tail.w, sizeof(flags));
+  return (flags & (uint32_t)HRT_PATH_DONE) == 0u ? 1u : 0u;
+}
+/* pixel i of the launch: add(acc, m2) is accum_paths.h add_paths on its records, or add_paths_in_place on its staged row */
+template <int FORMAT, class Add>
+__host__ __device__ inline void add_paths_pixel(const PathArgs& A, size_t i, Add&& add) {
+  const size_t d = A.n_tiles ? mapped_pixel(A.tiles, A.n_tiles, i) : i;
+  const float4 a = A.acc[d];
+  const Vec3 sum = add(v3(a.x, a.y, a.z), A.m2 ? A.m2 + d : nullptr);
+  A.acc[d] = make_float4(sum.x, sum.y, sum.z, 0.0f);
+  if constexpr (FORMAT >= 0) store_resolved<FORMAT>(A.out, d, sum, A.scale);
+}
+template <int FORMAT>
+__host__ __device__ inline void add_paths_pixel_global(const PathArgs& A, size_t i) {
+  const GlobalRecords records{A.paths + 3 * (i * A.samples)};
+  add_paths_pixel<FORMAT>(A, i, [&](Vec3 acc, float* m2) { return accum::add_paths(records, A.schedule, A.n_chunks, acc, m2); });
+}
+/* STAGED: a workgroup takes runs of A.run consecutive pixels.  It loads the last 16 bytes of the run's records with
+ * consecutive lanes on consecutive records (a wave instruction touches 24 cache lines, each once) into LDS rows of
+ * A.pitch slots, pitch odd, so the lanes of a ds_read_b128 group land on 16 different slots of the bank row; then one
+ * lane per pixel folds its row in order, chunk sum c into slot c of the row, and adds the pass from those slots.  Not STAGED (a pixel's records exceed the buffer): a lane walks its pixel's
+ * records in global memory.  Every loop is bounded by the pixel count, the samples or the chunks; no workgroup waits
+ * on another.  A wave adds its count of unfinished records with one atomic as it leaves, as step_kernel its rays. */
+template <int FORMAT, bool STAGED>
+__global__ __launch_bounds__(PATHS_BLOCK) void accumulate_paths(PathArgs A) {
+  uint32_t not_done = 0;
+  if constexpr (STAGED) {
+    __shared__ float4 stage[PATHS_STAGE];
+    const uint32_t S = A.samples, n_runs = (A.n_px + A.run - 1u) / A.run;
+    const uint32_t dq = PATHS_BLOCK / S, dk = PATHS_BLOCK - dq * S;
+    for (uint32_t r = blockIdx.x; r < n_runs; r += gridDim.x) {
+      const uint32_t px0 = r * A.run, cnt = min(A.run, A.n_px - px0), n_rec = cnt * S;
+      const float4* first = A.paths + 3 * ((size_t)px0 * S);
+      uint32_t q = threadIdx.x / S, k = threadIdx.x - q * S; /* record j of the run: sample k of its pixel q */
+      for (uint32_t j = threadIdx.x; j < n_rec; j += PATHS_BLOCK) {
+        const float4 tail = first[3 * (size_t)j + 2];
+        not_done += path_not_done(tail);
+        stage[q * A.pitch + k] = tail; /* q < cnt <= run, k < S <= pitch, run x pitch <= PATHS_STAGE */
+        q += dq;
+        k += dk;
+        if (k >= S) {
+          k -= S;
+          q++;
+        }
+      }
+      __syncthreads();
+      if (threadIdx.x < cnt) {
+        float4* row = stage + threadIdx.x * A.pitch;
+        add_paths_pixel<FORMAT>(A, (size_t)px0 + threadIdx.x,
+                                [&](Vec3 acc, float* m2) { return accum::add_paths_in_place(row, A.schedule, A.n_chunks, acc, m2); });
+      }
+      __syncthreads();
+    }
+  } else {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < A.n_px; i += (size_t)gridDim.x * blockDim.x) {
+      const GlobalRecords records{A.paths + 3 * (i * A.samples)};
+      if (A.live)
+        for (uint32_t k = 0; k < A.samples; k++) not_done += path_not_done(records(k));
+      add_paths_pixel_global<FORMAT>(A, i);
+    }
+  }
+  if (A.live) {
+    for (int o = 32; o > 0; o >>= 1) not_done += (uint32_t)__shfl_xor((int)not_done, o);
+    if ((threadIdx.x & 63u) == 0u && not_done != 0u) atomicAdd(A.live, not_done);
   }
 }
 
@@ -221,6 +314,23 @@ void resolve_pixels(int32_t format, const float4* acc, size_t n, float scale, vo
   hip_check(hipGetLastError(), "accum_resolve launch");
 }
 
+/* accumulate_paths over A.n_px > 0 pixels: staged while a pixel's row fits the buffer (rows of samples | 1 slots) */
+void launch_accumulate_paths(int format, PathArgs A, hipStream_t stream) {
+  A.pitch = A.samples | 1u;
+  A.run = A.pitch <= PATHS_STAGE ? std::min(PATHS_BLOCK, PATHS_STAGE / A.pitch) : 0u;
+  with_format<true>(format, [&](auto fc) {
+    constexpr int F = decltype(fc)::value;
+    if (F < 0) A.scale = 0.0f, A.out = nullptr;
+    if (A.run) {
+      const uint32_t n_runs = (A.n_px + A.run - 1u) / A.run;
+      hipLaunchKernelGGL((accumulate_paths<F, true>), dim3(std::min(n_runs, STREAM_MAX_BLOCKS)), dim3(PATHS_BLOCK), 0, stream, A);
+    } else {
+      hipLaunchKernelGGL((accumulate_paths<F, false>), dim3(stream_blocks(A.n_px)), dim3(PATHS_BLOCK), 0, stream, A);
+    }
+  });
+  hip_check(hipGetLastError(), "accumulate_paths launch");
+}
+
 /* what makes two passes samples of the same frame: everything of (camera, params) but samples and sample_offset */
 struct FrameIdentity {
   hrt_camera cam;
@@ -266,12 +376,13 @@ struct hrt_accum {
   uint32_t width = 0, height = 0;
   std::vector<hrt_tile> tiles;
   size_t n_px = 0;
-  /* The host copies of d_ntiles, d_ftiles and d_mtiles, which stream-ordered copies read.  Every device buffer below is an
+  /* The host copies of d_ntiles, d_ftiles, d_mtiles and d_ptiles, which stream-ordered copies read.  Every device buffer below is an
    * owning DevBuf, freed with the accumulator (hrt_accum_destroy); these are declared before them all, so they go after
    * them, when the frees have waited for the device. */
   std::vector<NoiseTile> h_ntiles;
   std::vector<filter::FilterTile> h_ftiles;
   std::vector<MergeTile> h_mtiles;
+  std::vector<G::TileDev> h_ptiles;
   DevBuf<float4> d_acc; /* n_px raw sums (x, y, z; w = 0), packed as the tiles are */
   bool has_identity = false;
   FrameIdentity identity;
@@ -301,6 +412,8 @@ struct hrt_accum {
   DevBuf<float> d_ferr;
   /* hrt_accum_merge_tiles' table of the selected tiles, made by the first such merge (host copy: h_mtiles) */
   DevBuf<MergeTile> d_mtiles;
+  /* hrt_accum_add_paths' tile map of a pass over a subset of the tiles, made by the first such pass (host copy: h_ptiles) */
+  DevBuf<G::TileDev> d_ptiles;
 };
 
 namespace {
@@ -574,18 +687,21 @@ uint64_t pass_chunks(const hrt_scene* s, const hrt_render_params* p) {
   return (uint64_t)n_head + n_tail;
 }
 
-/* A pass into every tile (idx null: hrt_accum_add, hrt_accum_add_resolve) or into tiles[idx[0..n)] alone
- * (hrt_accum_add_tiles): checks first (nothing changes on an error), then the shared launch */
-void accum_add(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, const uint32_t* idx, uint32_t n, int32_t format,
-               void* d_out, void* stream, hrt_render_stats* stats) {
+/* A pass into every tile (idx null: hrt_accum_add, hrt_accum_add_resolve, hrt_accum_add_paths) or into tiles[idx[0..n)]
+ * alone (hrt_accum_add_tiles, hrt_accum_add_paths): checks first (nothing changes on an error), then
+ * launch(tiles, n_tiles, dst, &launched), the one thing a rendered pass and a pass of caller-traced paths differ in, which
+ * makes its own checks before its first device call and sets launched once sums may have changed; then the ledger */
+template <class Launch>
+void accum_pass(const char* who, hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, const uint32_t* idx, uint32_t n,
+                int32_t format, void* d_out, Launch&& launch) {
   accum_usable(a);
-  if (d_out) accum_uniform(a, HRT_ERR_UNSUPPORTED, "hrt_accum_add_resolve: the accumulator's tiles hold different passes");
+  if (d_out) accum_uniform(a, HRT_ERR_UNSUPPORTED, (std::string(who) + ": the accumulator's tiles hold different passes").c_str());
   const size_t nt = a->tiles.size();
   std::vector<uint8_t> taken(idx ? nt : 0, 0);
   std::vector<hrt_tile> sub; /* the launch's tiles and where each lands in the accumulator */
   std::vector<uint32_t> offs;
   for (uint32_t i = 0; idx && i < n; i++) {
-    if (idx[i] >= nt || taken[idx[i]]) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_add_tiles: a tile index out of range or given twice"};
+    if (idx[i] >= nt || taken[idx[i]]) throw HipError{HRT_ERR_INVALID_ARG, std::string(who) + ": a tile index out of range or given twice"};
     taken[idx[i]] = 1;
     sub.push_back(a->tiles[idx[i]]);
     offs.push_back(a->tile_off[idx[i]]);
@@ -608,13 +724,66 @@ void accum_add(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, 
   }
   bool launched = false;
   try {
-    render_launch(a->scene, cam, p, idx ? sub.data() : a->tiles.data(), idx ? n : (uint32_t)nt, dst, stream, stats, &launched);
+    launch(idx ? sub.data() : a->tiles.data(), idx ? n : (uint32_t)nt, dst, &launched);
   } catch (...) {
     if (launched) a->invalid = true; /* the pass is (partly) in the sums and cannot be taken out again */
     throw;
   }
   adopt_identity(a, id);
   a->ledger.record(r, pass_chunks(a->scene, p), idx, n);
+}
+/* ... rendered (render.hip render_launch, which ends in accumulate_chunks) */
+void accum_add(const char* who, hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, const uint32_t* idx, uint32_t n,
+               int32_t format, void* d_out, void* stream, hrt_render_stats* stats) {
+  accum_pass(who, a, cam, p, idx, n, format, d_out, [&](const hrt_tile* tiles, uint32_t n_tiles, const SumsDest& dst, bool* launched) {
+    render_launch(a->scene, cam, p, tiles, n_tiles, dst, stream, stats, launched);
+  });
+}
+/* ... of the caller's paths (accumulate_paths): hrt_accum_add_paths after the checks that need no accumulator.
+ * batch(): the records and the live counter (or null) in device memory, asked for once every check has passed (the host
+ * variant makes them then); after(): what the call still does on the device once the kernel is enqueued (the host variant
+ * waits and reads the counter), so that a failure there leaves the accumulator marked as the sums are: changed */
+struct PathBatch {
+  const hrt_path* d_paths;
+  uint32_t* d_live;
+};
+template <class Batch, class After>
+void accum_add_paths(const char* who, hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, const uint32_t* idx, uint32_t n,
+                     Batch&& batch, After&& after, uint64_t n_paths, int32_t format, void* d_out, hipStream_t stream) {
+  accum_pass(who, a, cam, p, idx, n, format, d_out, [&](const hrt_tile* tiles, uint32_t n_tiles, const SumsDest& dst, bool* launched) {
+    check_render_params(cam, p);
+    uint64_t n_px = 0;
+    for (uint32_t i = 0; i < n_tiles; i++) n_px += (uint64_t)tiles[i].w * tiles[i].h;
+    if (n_paths >= (1ull << 32) || n_paths != n_px * p->samples)
+      throw HipError{HRT_ERR_INVALID_ARG, std::string(who) + ": n_paths is not (the tiles' pixels) x samples, or not below 2^32"};
+    uint32_t chunk = 0, n_head = 0, first = 0, n_tail = 0;
+    chunk_schedule(a->scene, p, chunk, n_head, first, n_tail);
+    PathArgs A;
+    memset(&A, 0, sizeof(A));
+    A.acc = dst.d_acc, A.m2 = dst.d_m2;
+    A.out = dst.d_preview, A.scale = dst.preview_scale;
+    A.n_px = (uint32_t)n_px, A.samples = p->samples, A.n_chunks = n_head + n_tail;
+    A.schedule = accum::PathSchedule{chunk, n_head, first};
+    DeviceGuard dg(a->device);
+    const PathBatch b = batch();
+    A.paths = reinterpret_cast<const float4*>(b.d_paths), A.live = b.d_live;
+    if (dst.acc_offs) { /* a subset: launched tile i is the accumulator's tile at acc_offs[i] (mapped_pixel reads the two offsets) */
+      std::vector<G::TileDev> td(n_tiles);
+      uint32_t off = 0;
+      for (uint32_t i = 0; i < n_tiles; i++) {
+        td[i] = G::TileDev{tiles[i].x, tiles[i].y, tiles[i].w, tiles[i].h, (tiles[i].w + 7) / 8, 0u, off, dst.acc_offs[i]};
+        off += tiles[i].w * tiles[i].h;
+      }
+      if (!a->d_ptiles.p) a->d_ptiles.alloc(a->tiles.size() * sizeof(G::TileDev), "hipMalloc(path tiles)");
+      a->h_ptiles.swap(td); /* stays alive with the accumulator, as h_mtiles does */
+      hip_check(hipMemcpyAsync(a->d_ptiles.p, a->h_ptiles.data(), n_tiles * sizeof(G::TileDev), hipMemcpyHostToDevice, stream),
+                "hipMemcpyAsync(path tiles)");
+      A.tiles = a->d_ptiles.p, A.n_tiles = n_tiles;
+    }
+    launch_accumulate_paths(dst.preview, A, stream);
+    *launched = true;
+    after();
+  });
 }
 
 /* A merge's preconditions beyond usable, in the order they are refused in: the same noise plane or none, uniform on
@@ -775,7 +944,7 @@ hrt_status hrt_accum_add(hrt_accum* a, const hrt_camera* cam, const hrt_render_p
                          hrt_render_stats* stats) {
   return hguard([&] {
     if (!a || !cam || !p) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_add: null argument"};
-    accum_add(a, cam, p, nullptr, 0, -1, nullptr, stream, stats);
+    accum_add("hrt_accum_add", a, cam, p, nullptr, 0, -1, nullptr, stream, stats);
   });
 }
 
@@ -784,7 +953,7 @@ hrt_status hrt_accum_add_resolve(hrt_accum* a, const hrt_camera* cam, const hrt_
   return hguard([&] {
     if (!a || !cam || !p || !d_out) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_add_resolve: null argument"};
     accum_format(format);
-    accum_add(a, cam, p, nullptr, 0, format, d_out, stream, stats);
+    accum_add("hrt_accum_add_resolve", a, cam, p, nullptr, 0, format, d_out, stream, stats);
   });
 }
 
@@ -807,7 +976,56 @@ hrt_status hrt_accum_add_tiles(hrt_accum* a, const hrt_camera* cam, const hrt_re
                                void* stream, hrt_render_stats* stats) {
   return hguard([&] {
     if (!a || !cam || !p || !idx || n == 0) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_add_tiles: null argument or no tiles"};
-    accum_add(a, cam, p, idx, n, -1, nullptr, stream, stats);
+    accum_add("hrt_accum_add_tiles", a, cam, p, idx, n, -1, nullptr, stream, stats);
+  });
+}
+
+/* the checks of hrt_accum_add_paths{,_host} that need no accumulator state */
+static void add_paths_args(const char* who, const hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, const uint32_t* idx,
+                           uint32_t n_idx, const hrt_path* paths, uint64_t n_paths, int32_t format, const void* d_out) {
+  const auto refuse = [who](const char* why) { throw HipError{HRT_ERR_INVALID_ARG, std::string(who) + why}; };
+  if (!a || !cam || !p || !paths) refuse(": null argument");
+  if ((idx != nullptr) != (n_idx != 0)) refuse(": a tile list needs both idx and n_idx");
+  if (n_paths >= (1ull << 32)) refuse(": n_paths must be below 2^32");
+  if (format != -1) accum_format(format);
+  if (format >= 0 && !d_out) refuse(": a preview format needs d_out");
+  if (format >= 0 && idx) refuse(": a pass over a subset of the tiles has no preview");
+}
+
+hrt_status hrt_accum_add_paths(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, const uint32_t* idx, uint32_t n_idx,
+                               const hrt_path* d_paths, uint64_t n_paths, int32_t format, void* d_out, uint32_t* d_live, void* stream) {
+  return hguard([&] {
+    add_paths_args("hrt_accum_add_paths", a, cam, p, idx, n_idx, d_paths, n_paths, format, d_out);
+    if (!aligned16(d_paths)) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_add_paths: the records must be 16-byte aligned"};
+    if (((uintptr_t)d_live & 3u) != 0) throw HipError{HRT_ERR_INVALID_ARG, "hrt_accum_add_paths: d_live must be 4-byte aligned"};
+    accum_add_paths("hrt_accum_add_paths", a, cam, p, idx, n_idx, [&] { return PathBatch{d_paths, d_live}; }, [] {}, n_paths, format,
+                    format >= 0 ? d_out : nullptr, (hipStream_t)stream);
+  });
+}
+
+hrt_status hrt_accum_add_paths_host(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p, const uint32_t* idx, uint32_t n_idx,
+                                    const hrt_path* paths, uint64_t n_paths, uint32_t* live) {
+  return hguard([&] {
+    add_paths_args("hrt_accum_add_paths_host", a, cam, p, idx, n_idx, paths, n_paths, -1, nullptr);
+    /* both run inside the pass, under its device guard, once every check has passed: the copies in, then the wait and
+     * the counter; the buffers go before the guard does */
+    DevBuf<hrt_path> d_paths;
+    DevBuf<uint32_t> d_live;
+    const auto copy_in = [&] {
+      const uint32_t zero = 0;
+      if (live) d_live = DevBuf<uint32_t>(sizeof(uint32_t), &zero);
+      d_paths = DevBuf<hrt_path>((size_t)n_paths * sizeof(hrt_path), paths);
+      return PathBatch{d_paths.p, d_live.p};
+    };
+    const auto wait = [&] {
+      hip_check(hipStreamSynchronize(nullptr), "hipStreamSynchronize(paths)");
+      uint32_t counted = 0;
+      if (live) hip_check(hipMemcpy(&counted, d_live.p, sizeof(counted), hipMemcpyDeviceToHost), "hipMemcpy(live count)");
+      d_paths = DevBuf<hrt_path>();
+      d_live = DevBuf<uint32_t>();
+      if (live) *live += counted;
+    };
+    accum_add_paths("hrt_accum_add_paths_host", a, cam, p, idx, n_idx, copy_in, wait, n_paths, -1, nullptr, nullptr);
   });
 }
 
@@ -1299,6 +1517,68 @@ hrt_status hrt_debug_noise(int32_t on_device, const float* partial, const uint32
     hip_check(hipMemcpy(m2_inout, d_m2.p, m_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
     hip_check(hipMemcpy(err_out, d_err.p, m_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
     hip_check(hipMemcpy(mean_max_out, d_rec.p, sizeof(float2), hipMemcpyDeviceToHost), "hipMemcpy");
+  });
+}
+
+hrt_status hrt_debug_accum_paths(int32_t on_device, const hrt_path* paths, uint32_t n_px, uint32_t samples, const uint32_t* sched3,
+                                 float* acc_inout, float* m2_inout, uint64_t total_samples, int32_t format, void* out,
+                                 uint32_t* live_out) {
+  return hguard([&] {
+    if (!paths || !sched3 || !acc_inout || samples == 0 || (uint64_t)n_px * samples >= (1ull << 32) || format < -1 ||
+        format > HRT_ACCUM_RGBA8 || (format >= 0 && (!out || total_samples == 0 || total_samples > (1ull << 32))))
+      throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_accum_paths: bad argument"};
+    /* the schedule must cut [0, samples) into chunks that are not empty: K is where they end */
+    const accum::PathSchedule schedule{sched3[0], sched3[1], sched3[2]};
+    uint32_t n_chunks = 0;
+    for (uint32_t end = 0; end != samples; n_chunks++) {
+      uint32_t s0 = 0, s1 = 0;
+      if (schedule.chunk_head != 0) schedule.range(n_chunks, s0, s1);
+      if (s0 != end || s1 <= s0 || s1 > samples) throw HipError{HRT_ERR_INVALID_ARG, "hrt_debug_accum_paths: not a schedule of `samples` samples"};
+      end = s1;
+    }
+    if (live_out) *live_out = 0;
+    if (n_px == 0) return;
+    const G::TileDev map{0, 0, n_px, 1, (n_px + 7) / 8, 0, 0, 0}; /* one tile: the launch's pixels onto themselves */
+    PathArgs A;
+    memset(&A, 0, sizeof(A));
+    A.scale = format >= 0 ? accum::resolve_scale(total_samples) : 0.0f;
+    A.n_tiles = 1;
+    A.n_px = n_px, A.samples = samples, A.n_chunks = n_chunks;
+    A.schedule = schedule;
+    const size_t n = (size_t)n_px * samples;
+    const size_t out_bytes = format < 0 ? 0 : (size_t)n_px * (format == HRT_ACCUM_F32 ? 16u : 4u);
+    if (!on_device) {
+      A.paths = reinterpret_cast<const float4*>(paths);
+      A.acc = reinterpret_cast<float4*>(acc_inout), A.m2 = m2_inout, A.out = out, A.tiles = &map;
+      with_format<true>(format, [&](auto fc) {
+        for (size_t i = 0; i < n_px; i++) add_paths_pixel_global<decltype(fc)::value>(A, i);
+      });
+      for (size_t j = 0; live_out && j < n; j++) *live_out += path_not_done(A.paths[3 * j + 2]);
+      return;
+    }
+    /* the real kernel on the calling thread's current device, and the separate resolve of the same sums, which must
+     * agree with the fused one */
+    const size_t a_bytes = (size_t)n_px * sizeof(float4), m_bytes = (size_t)n_px * sizeof(float);
+    const uint32_t zero = 0;
+    DevBuf<float4> d_paths(n * sizeof(hrt_path), paths), d_acc(a_bytes, acc_inout);
+    DevBuf<float> d_m2(m_bytes, m2_inout);
+    DevBuf<uint8_t> d_out(out_bytes + 16), d_out2(out_bytes + 16);
+    DevBuf<G::TileDev> d_map(sizeof(G::TileDev), &map);
+    DevBuf<uint32_t> d_live(sizeof(uint32_t), &zero);
+    A.paths = d_paths.p;
+    A.acc = d_acc.p, A.m2 = m2_inout ? d_m2.p : nullptr, A.out = d_out.p, A.tiles = d_map.p;
+    A.live = live_out ? d_live.p : nullptr;
+    launch_accumulate_paths(format, A, nullptr);
+    hip_check(hipMemcpy(acc_inout, d_acc.p, a_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+    if (m2_inout) hip_check(hipMemcpy(m2_inout, d_m2.p, m_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+    if (live_out) hip_check(hipMemcpy(live_out, d_live.p, sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy");
+    if (format < 0) return;
+    resolve_pixels(format, d_acc.p, n_px, A.scale, d_out2.p, nullptr);
+    std::vector<uint8_t> second(out_bytes);
+    hip_check(hipMemcpy(out, d_out.p, out_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+    hip_check(hipMemcpy(second.data(), d_out2.p, out_bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+    if (memcmp(out, second.data(), out_bytes) != 0)
+      throw HipError{HRT_ERR_STATE, "hrt_debug_accum_paths: accumulate_paths' fused resolve and accum_resolve differ"};
   });
 }
 

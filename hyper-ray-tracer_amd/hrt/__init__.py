@@ -237,7 +237,8 @@ OPTIONAL = {"hrt_abi_version", "hrt_last_launch", "hrt_debug_box_test", "hrt_sce
             "hrt_accum_noise_filtered", "hrt_debug_noise_filtered",
             "hrt_scene_intersect", "hrt_scene_intersect_host", "hrt_camera_rays", "hrt_camera_rays_host",
             "hrt_scene_scatter", "hrt_scene_scatter_host", "hrt_camera_paths", "hrt_camera_paths_host",
-            "hrt_scene_step", "hrt_scene_step_host"}
+            "hrt_scene_step", "hrt_scene_step_host",
+            "hrt_accum_add_paths", "hrt_accum_add_paths_host", "hrt_debug_accum_paths"}
 HRT_LIB_OVERRIDE = bool(os.environ.get("HRT_LIB"))
 
 # Every entry point of include/hrt/hrt.h (tests/test_abi.py checks the header against this list).
@@ -266,6 +267,7 @@ EXPORTS = [
     "hrt_scene_intersect", "hrt_scene_intersect_host", "hrt_camera_rays", "hrt_camera_rays_host",
     "hrt_scene_scatter", "hrt_scene_scatter_host", "hrt_camera_paths", "hrt_camera_paths_host",
     "hrt_scene_step", "hrt_scene_step_host",
+    "hrt_accum_add_paths", "hrt_accum_add_paths_host", "hrt_debug_accum_paths",
 ]
 
 ABI_VERSION = 6  # include/hrt/hrt.h HRT_ABI_VERSION: the struct layouts below
@@ -395,6 +397,9 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         "hrt_camera_paths_host": (S, [vp, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams), vp, u32, vp, vp]),
         "hrt_scene_step": (S, [vp, ctypes.POINTER(StepParams), vp, vp, u64, vp, ctypes.POINTER(PathList), ctypes.POINTER(PathList), vp, vp]),
         "hrt_scene_step_host": (S, [vp, ctypes.POINTER(StepParams), vp, vp, u64, vp, ctypes.POINTER(u64)]),
+        "hrt_accum_add_paths": (S, [vp, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams), vp, u32, vp, u64, i32, vp, vp, vp]),
+        "hrt_accum_add_paths_host": (S, [vp, ctypes.POINTER(Camera), ctypes.POINTER(RenderParams), vp, u32, vp, u64, _U32P]),
+        "hrt_debug_accum_paths": (S, [i32, vp, u32, u32, vp, vp, vp, u64, i32, vp, _U32P]),
     }
     for name, (res, args) in sig.items():
         if name in OPTIONAL and HRT_LIB_OVERRIDE and not hasattr(L, name):
@@ -829,9 +834,15 @@ def trace_paths_fused(scene: "Scene", cam: Camera, p: RenderParams, tiles=None, 
     device, `steps` rounds per call.  The live count is read back every `check_every` calls only (0: never, the loop then
     makes all ceil(p.max_depth / steps) calls, the late ones over an empty list), the ray count once at the end.  Returns
     what trace_paths returns, bit for bit."""
+    rays, paths = camera_paths(scene, cam, p, tiles, device=True)
+    n_rays = _step_to_completion(scene, cam, p, rays, paths, steps, check_every)
+    return (paths if device else paths[:, 8:11].cpu().numpy()), n_rays
+
+
+def _step_to_completion(scene: "Scene", cam: Camera, p: RenderParams, rays, paths, steps: int, check_every: int) -> int:
+    """trace_paths_fused's loop on device tensors of rays and paths, in place; returns the rays traced."""
     import torch
 
-    rays, paths = camera_paths(scene, cam, p, tiles, device=True)
     n = rays.shape[0]
     lists = [(torch.empty(n, dtype=torch.int32, device=rays.device), torch.zeros(1, dtype=torch.int32, device=rays.device))
              for _ in range(2)]
@@ -844,7 +855,7 @@ def trace_paths_fused(scene: "Scene", cam: Camera, p: RenderParams, tiles=None, 
         live = out
         if check_every and (call + 1) % check_every == 0 and int(out[1]) == 0:
             break
-    return (paths if device else paths[:, 8:11].cpu().numpy()), int(n_rays)
+    return int(n_rays)
 
 
 def tile_grid(width: int, height: int, tile_size: int = 80, rank: int = 0, world: int = 1) -> List[Tuple[int, int, int, int]]:
@@ -1003,6 +1014,54 @@ class Accumulator:
         stream.synchronize()
         img = self._shaped(buf.cpu().numpy())
         return (img, st) if stats else img
+
+    def add_paths(self, paths, cam: Camera, p: RenderParams, tiles=None, preview=None, live: bool = False):
+        """Add the radiance of caller-traced paths as ONE pass, bit for bit what `add` with the same arguments adds when
+        the paths are the render's (hrt_accum_add_paths): samples [p.sample_offset, + p.samples) of every pixel, or of
+        the tiles `tiles` indexes into self.tiles.  paths: the batch hrt.camera_paths(scene, cam, p, those tiles in that
+        order) starts, stepped by the caller: an (n, 12) float32 CUDA tensor, or a PATH_DTYPE numpy array, which takes
+        the host variant (no preview).  A record's radiance is added whatever its flags; live=True also returns how many
+        records were not DONE.  Returns what `add` returns (None or the preview), with live=True (that, count)."""
+        idx = None if tiles is None else np.ascontiguousarray(list(tiles), np.uint32)
+        ip, ni = (None, 0) if idx is None else (idx.ctypes.data if idx.size else None, idx.size)
+        want = preview is not None and preview is not False
+        if isinstance(paths, np.ndarray):
+            if want:
+                raise ValueError("the host variant has no preview: pass a CUDA tensor")
+            if paths.dtype != PATH_DTYPE or not paths.flags.c_contiguous:
+                raise ValueError("paths: a contiguous PATH_DTYPE array")
+            count = ctypes.c_uint32(0)
+            _check(load().hrt_accum_add_paths_host(self.h, ctypes.byref(cam), ctypes.byref(p), ip, ni, paths.ctypes.data, paths.size,
+                                                   ctypes.byref(count) if live else None))
+            return (None, count.value) if live else None
+        import torch
+
+        if not (isinstance(paths, torch.Tensor) and paths.is_cuda and paths.is_contiguous() and
+                paths.numel() * paths.element_size() % 48 == 0):
+            raise ValueError("paths: a PATH_DTYPE array, or a contiguous CUDA tensor of 48-byte records")
+        n = paths.numel() * paths.element_size() // 48
+        count = torch.zeros(1, dtype=torch.int32, device=paths.device) if live else None
+        fmt = "f32" if preview is True else preview
+        buf = torch.empty(self.n_pixels * 4, dtype=torch.float32 if fmt == "f32" else torch.uint8, device=paths.device) if want else None
+        _check(load().hrt_accum_add_paths(self.h, ctypes.byref(cam), ctypes.byref(p), ip, ni, paths.data_ptr(), n,
+                                          _ACCUM_FORMATS[fmt] if want else -1, buf.data_ptr() if want else None,
+                                          count.data_ptr() if live else None, None))
+        img = self._shaped(buf.cpu().numpy()) if want else None
+        return (img, int(count)) if live else img
+
+    def add_wavefront(self, cam: Camera, p: RenderParams, tiles=None, steps: int = 2, check_every: int = 4, preview=None) -> int:
+        """`add` by another route, and the template of a caller's own integrator: hrt.camera_paths on the tiles, then
+        hrt.trace_paths_fused's loop (Scene.step over two device-side live lists), then `add_paths`.  The accumulator
+        ends bit for bit where add(cam, p, tiles=tiles) leaves it.  Returns the rays traced (the render's
+        RenderStats.segments); with a preview, (preview, rays).
+        Memory: the batch holds a 48-byte ray and a 48-byte path per sample of the pass, 96 bytes per path, plus two
+        4-byte live-list entries.  How many samples go into one pass is the caller's choice and part of the result:
+        splitting a pass changes the pass schedule (hrt.sample_chunks) and so the frame's bits, exactly as it does for `add`."""
+        sub = None if tiles is None else [self.tiles[i] for i in tiles]
+        rays, paths = camera_paths(self.scene, cam, p, self.tiles if sub is None else sub, device=True)
+        n_rays = _step_to_completion(self.scene, cam, p, rays, paths, steps, check_every)
+        img = self.add_paths(paths, cam, p, tiles=tiles, preview=preview)
+        return n_rays if img is None else (img, n_rays)
 
     @property
     def samples(self) -> int:
@@ -1309,6 +1368,30 @@ def debug_accumulate(partial: np.ndarray, acc: np.ndarray, samples: int = 0, fmt
     _check(load().hrt_debug_accumulate(1 if on_device else 0, pa.ctypes.data, n_chunks, n, a.ctypes.data, int(samples),
                                        -1 if fmt is None else _ACCUM_FORMATS[fmt], None if out is None else out.ctypes.data))
     return a, out
+
+
+def debug_accum_paths(paths: np.ndarray, samples: int, schedule, acc: np.ndarray, m2=None, total_samples: int = 0,
+                      fmt: Optional[str] = None, on_device: bool = False):
+    """hrt_debug_accum_paths: csrc/accum_paths.h on the host, or the real kernel on the current device.  paths: a
+    PATH_DTYPE array of n_px x samples records, a pixel's consecutive; schedule: hrt.sample_chunks' dict or its
+    (chunk, head, first); acc (n_px, 4) / m2 (n_px,) or None: the sums and moments before the pass.  Returns (acc, m2 or
+    None after the pass, the frame of total_samples samples in `fmt` or None, the records that are not DONE)."""
+    pa = np.ascontiguousarray(paths, PATH_DTYPE).reshape(-1)
+    n_px = pa.size // samples
+    if n_px * samples != pa.size:
+        raise ValueError("paths: n_px x samples records")
+    if isinstance(schedule, dict):
+        schedule = (schedule["chunk"], schedule["head"], schedule["first"])
+    sch = np.array(schedule, np.uint32)[:3].copy()
+    a = np.array(acc, np.float32).reshape(n_px, 4).copy()
+    m = None if m2 is None else np.array(m2, np.float32).reshape(n_px).copy()
+    out = None if fmt is None else np.zeros((n_px, 4), np.float32 if fmt == "f32" else np.uint8)
+    live = ctypes.c_uint32(0)
+    _check(load().hrt_debug_accum_paths(1 if on_device else 0, pa.ctypes.data if pa.size else None, n_px, int(samples), sch.ctypes.data,
+                                        a.ctypes.data if a.size else None, None if m is None else m.ctypes.data, int(total_samples),
+                                        -1 if fmt is None else _ACCUM_FORMATS[fmt], None if out is None else out.ctypes.data,
+                                        ctypes.byref(live)))
+    return a, m, out, live.value
 
 
 def debug_noise(partial: np.ndarray, sizes, acc: np.ndarray, m2: np.ndarray, samples: int, chunks: int, floor: float = 0.05,

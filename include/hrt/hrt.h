@@ -948,6 +948,54 @@ hrt_status hrt_scene_step(hrt_scene* s, const hrt_step_params* sp, hrt_ray* d_ra
 hrt_status hrt_scene_step_host(hrt_scene* s, const hrt_step_params* sp, hrt_ray* rays, hrt_path* paths, uint64_t n,
                                hrt_hit* hits /* may be NULL */, uint64_t* n_rays /* may be NULL */);
 
+/* ---- caller-traced paths into an accumulator ----
+ * hrt_accum_add_paths reduces a finished batch of paths into an accumulator exactly as hrt_accum_add would have added the
+ * same samples, so a wavefront loop built on the calls above ends in the accumulator's products: resolve, the noise
+ * estimate and refinement, the filters, snapshots and per-tile merges cannot tell the two routes apart.
+ *
+ *   1. The batch is packed as hrt_camera_paths packs it: with S = p->samples, path (launch pixel i) * S + k is sample
+ *      p->sample_offset + k of that pixel, the launch's pixels being those of the accumulator's tiles in order (idx NULL) or
+ *      of tiles[idx[0]], tiles[idx[1]], ... .
+ *   2. Arithmetic (csrc/accum_paths.h; none of it new).  For each chunk c of the pass's schedule (hrt_debug_sample_chunks)
+ *      the chunk sum starts from (0, 0, 0) and adds the radiance of the chunk's paths in sample order, as the render kernels
+ *      sum a chunk's samples; the chunk sums then go where a rendered pass's go: the pass sum is the chunk sums added in
+ *      chunk order starting from chunk 0's, acc = acc + pass_sum, and with HRT_ACCUM_NOISE m2 = m2 + pass_moment over the
+ *      same chunk sums.  A record's radiance is taken as the three floats it holds WHATEVER its flags: an INVALID path's, a
+ *      NaN, the radiance of a path the caller stopped early.  What a custom integrator deposits is its own business.
+ *   3. Bit contract with hrt_accum_add / hrt_accum_add_tiles.  Take a committed scene, a camera and params whose flags
+ *      select no approximate culling; start the paths with hrt_camera_paths on the same tiles in the same order and step
+ *      them to completion with hrt_scene_step or the intersect / scatter pair.  This call then leaves the accumulator in
+ *      the state the render call with the same arguments leaves it in: sums, noise plane, per-tile sample ranges and chunk
+ *      counts K, frame identity; the preview is hrt_accum_add_resolve's.  The scatter contract's exclusion carries over: a
+ *      path that met a non-finite hit.
+ *   4. Host bookkeeping is hrt_accum_add's own (one function): the identity check and adoption, the range check before
+ *      anything is launched, the ledger's record after.
+ *   5. What a result depends on.  A pixel after the call is a function of its sums before, its own S records and the
+ *      schedule ALONE: never of the tile subset, of the launch shape or of the device.
+ *   6. d_live, when given: the call ADDS the number of records that are not HRT_PATH_DONE, which is how a caller learns
+ *      without a host round trip that it deposited unfinished paths.  They are deposited all the same.  The caller zeroes it.
+ *   7. One kernel launch, asynchronous on `stream`, no intermediate buffer.  A pass over a subset keeps its tile map in the
+ *      accumulator, as hrt_accum_merge_tiles keeps its table: one accumulator takes its passes from one thread at a time.
+ * Errors, each changing nothing and answered before any device call: HRT_ERR_INVALID_ARG for a null accumulator, camera,
+ * params or paths, idx without n_idx or n_idx without idx, n_paths that is not (the tiles' pixels) x p->samples or is
+ * >= 2^32, d_paths not 16-byte or d_live not 4-byte aligned, a format outside {-1, HRT_ACCUM_F32, HRT_ACCUM_RGBA8}, a
+ * format >= 0 with a null d_out or with idx (a pass over a subset has no preview); hrt_accum_add_tiles' refusals for idx
+ * and hrt_accum_add's for the identity, the sample range and the params; HRT_ERR_UNSUPPORTED for a preview when the
+ * tiles hold different passes; HRT_ERR_STATE for an accumulator that holds an incomplete pass. */
+/* Add the radiance of caller-traced paths as ONE pass: samples [p->sample_offset, + p->samples) of every pixel of the
+ * accumulator's tiles (idx NULL) or of tiles[idx[0..n_idx)] alone.  d_paths: the batch hrt_camera_paths(s, cam, p, those
+ * tiles in that order) starts, n_paths = (their pixels) x p->samples records, 16-byte aligned, read only. */
+hrt_status hrt_accum_add_paths(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p,
+                               const uint32_t* idx /* may be NULL */, uint32_t n_idx,
+                               const hrt_path* d_paths, uint64_t n_paths,
+                               int32_t format /* -1: no preview */, void* d_out /* may be NULL */,
+                               uint32_t* d_live /* may be NULL: ADDS the records that are not PATH_DONE */,
+                               void* stream);
+/* ... with the paths in HOST memory: copies in, runs the device path, synchronous; *live is added to */
+hrt_status hrt_accum_add_paths_host(hrt_accum* a, const hrt_camera* cam, const hrt_render_params* p,
+                                    const uint32_t* idx, uint32_t n_idx, const hrt_path* paths, uint64_t n_paths,
+                                    uint32_t* live /* may be NULL */);
+
 /* ---- diagnostics ---- */
 /* Device occupancy / layout facts of the committed scene (for DESIGN/bench). */
 typedef struct hrt_scene_info {
@@ -1062,6 +1110,16 @@ hrt_status hrt_debug_accumulate(int32_t on_device, const float* partial, uint32_
 hrt_status hrt_debug_noise(int32_t on_device, const float* partial, const uint32_t* sizes, uint32_t n_chunks, uint32_t n,
                            float* acc_inout, float* m2_inout, uint64_t samples, uint64_t chunks, float floor, float* err_out,
                            float* mean_max_out);
+/* hrt_accum_add_paths' arithmetic (csrc/accum_paths.h) for n_px pixels of `samples` paths each, packed pixel-major, with
+ * the same code compiled for the host (on_device = 0; no device involved) or through the real kernel on one
+ * identity-mapped tile (1: the calling thread's current HIP device).  sched3 = (chunk, head chunks, samples of the first
+ * chunk), the first three words of hrt_debug_sample_chunks; it must cut [0, samples) into chunks.  acc_inout (n_px x 4 f32)
+ * and m2_inout (n_px f32, or NULL: no noise plane) are the sums and moments before and after the pass; out the frame of
+ * total_samples samples in an HRT_ACCUM_* format after it (format -1: none), which on the device must equal accum_resolve
+ * of the same sums; *live_out (may be NULL) takes the number of records that are not HRT_PATH_DONE. */
+hrt_status hrt_debug_accum_paths(int32_t on_device, const hrt_path* paths, uint32_t n_px, uint32_t samples, const uint32_t* sched3,
+                                 float* acc_inout, float* m2_inout, uint64_t total_samples, int32_t format, void* out,
+                                 uint32_t* live_out);
 /* The noise plane of a HRT_ACCUM_NOISE accumulator (n_pixels f32, packed as the tiles are) into host memory, after a
  * device synchronisation: for the tests that hold m2 to its bit contract. */
 hrt_status hrt_debug_accum_moments(hrt_accum* a, float* m2_out);
